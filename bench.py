@@ -17,6 +17,12 @@ keeps 2^20 steps per GPU instead).  The segments are stitched by two all-gathers
 over RCCL, issued by libpgps itself on the context's stream (pgps_pkfs_seg_dev_f64; `--exchange torch`
 runs the older torch.distributed-hosted variant).
 
+A plain run sets up, warms up, times --steps passes and prints the JSON line (`value`, `ms_per_step`: wall time of the
+timed region).  `--full` adds what takes runs of its own: the per-kernel breakdown and roofline (with the dominant kernel's
+launches event-stamped inside the timed region), the fused / LTI side legs, the CPU baselines and the parity check against
+the CPU oracle, the one-GPU reference of the strong-scaling line and the all-gather latency.  `--dump-outputs DIR` writes
+what the last timed pass computed as .npy files (the inputs are seeded: the same arguments give the same inputs).
+
 `python bench.py --gpus N` works unaided: without a launcher's WORLD_SIZE in the environment the parent
 -- before it imports torch or touches the GPU -- starts `python -m torch.distributed.run` with N fresh
 child processes and relays rank 0's JSON line.
@@ -51,6 +57,7 @@ for p in (ROOT, os.path.join(ROOT, "parallel-gps_amd")):
 HBM_PEAK_GBPS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.3 TB/s achievable)
 # vector (non-MFMA) FMA peaks, SURVEY.md 8(d): the path has no dense contraction, the matrix cores never apply
 VECTOR_PEAK_TFLOPS = {"f64": 78.6, "f32": 157.3}
+DUMP_BYTES = 60 * 10 ** 6      # --dump-outputs: .npy files of one run, all ranks together (under 64 MB either way)
 
 
 def parse():
@@ -97,9 +104,9 @@ def parse():
                          "one device, so this implies --exchange torch --dist-backend gloo)")
     ap.add_argument("--force-segments", action="store_true",
                     help="run the multi-GPU segment protocol even at one GPU (measures its overhead)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--main-only", action="store_true",
-                    help="skip the fused / LTI side legs (profiling runs: only the measured path's kernels are launched)")
+                    help="--full without the fused / LTI side legs (profiling runs: only the measured path's kernels are launched)")
     ap.add_argument("--event-every", type=int, default=8,
                     help="hipEvent-time every n-th launch of the dominant kernel inside the timed region")
     ap.add_argument("--nan-frac", type=float, default=0.0)
@@ -109,6 +116,15 @@ def parse():
     ap.add_argument("--f32-policy", type=int, default=0, choices=[0, 1, 2],
                     help="float32 series: 0 automatic promotion to fp64 arithmetic on dense grids, 1 never, 2 always "
                          "(pgps_set_f32_policy)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: per-kernel timings and roofline, the fused / LTI side legs, "
+                         "the CPU baselines and the parity check against the CPU oracle, the one-GPU reference of the "
+                         "strong-scaling line and the all-gather latency (without it a run sets up, warms up, times --steps "
+                         "passes and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region write what its last pass computed as DIR/<name>.npy (the filtered and "
+                         f"smoothed moments and the log-likelihood, at most {DUMP_BYTES // 10 ** 6} MB in all: a fixed, seeded "
+                         "sample of the time steps, listed in sample_rows.npy, where the whole arrays do not fit)")
     args = ap.parse_args()
     if args.scaling == "auto":
         args.scaling = "strong" if args.gpus > 1 else "weak"
@@ -401,6 +417,29 @@ def committed_traffic(key, slot):
     return None, None, None
 
 
+def dump_outputs(dirname, per_step, scalars, n, budget, suffix=""):
+    """--dump-outputs: the arrays a caller of the timed path receives, as DIR/<name><suffix>.npy in their own precision
+    (float32 / float64).  per_step: name -> device tensor with one row per time step; scalars: name -> device tensor.  Where
+    the whole arrays exceed `budget` bytes, the same fixed, seeded sample of rows is taken from each of them (sorted, and
+    written as sample_rows<suffix>.npy in float64)."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    header = 4096                                            # .npy headers and the scalars, generously
+    row_bytes = sum(t[0].numel() * t.element_size() for t in per_step.values())
+    budget -= header * (len(per_step) + len(scalars) + 1)
+    idx = None
+    if row_bytes * n > budget:
+        k = max(1, budget // (row_bytes + 8))
+        rows = np.sort(np.random.default_rng(20240601).choice(n, size=k, replace=False))
+        np.save(os.path.join(dirname, f"sample_rows{suffix}.npy"), rows.astype(np.float64))
+        idx = torch.from_numpy(rows).to(next(iter(per_step.values())).device)
+    for name, t in per_step.items():
+        a = t if idx is None else t.index_select(0, idx)
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a.cpu().numpy())
+    for name, t in scalars.items():
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), t.cpu().numpy())
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -506,7 +545,7 @@ def main():
     ll_d = torch.zeros((2,), dtype=torch.float64, device=dev)
 
     rccl_info, exchange_fallback, one_gpu_ms = None, False, None
-    if world > 1 and args.scaling == "strong" and args.path == "lgssm":
+    if args.full and world > 1 and args.scaling == "strong" and args.path == "lgssm":
         # the reference of the strong-scaling factor: the SAME series length on ONE GPU (rank 0), outside the timed
         # region, before any communicator exists; the other ranks wait at the barrier
         if rank == 0:
@@ -576,7 +615,8 @@ def main():
             n_rccl, r_rccl = ctx.comm_count()       # what RCCL itself says (ncclCommCount / ncclCommUserRank)
             if (n_rccl, r_rccl) != (world, rank):
                 raise SystemExit(f"RCCL communicator reports {n_rccl} ranks / rank {r_rccl}, expected {world} / {rank}")
-            rccl_info = {"in_library": True, "ranks": n_rccl, "allgather_us": allgather_latency(ctx, d, dtype_t, dev, stream, world),
+            rccl_info = {"in_library": True, "ranks": n_rccl,
+                         "allgather_us": allgather_latency(ctx, d, dtype_t, dev, stream, world) if args.full else None,
                          "library": _backend.Context.comm_library()}
 
             def step():
@@ -616,29 +656,30 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(dev)
-    # which launch slot dominates a pass: measured (events around every launch of a short untimed run), not assumed
-    n_probe = max(3, min(args.warmup, 10))
-    ctx.profile_read(reset=True)
-    ctx.profile_sample(1)
-    ctx.profile_enable(SLOT_MASK)
-    for _ in range(n_probe):
-        step()
-    probe = ctx.profile_read(reset=True)
-    ctx.profile_enable(0)
-    # (only slots whose kernels touch bytes of the contract can be priced against it: the cooperative families' scan slots cannot)
-    fam_probe = ctx.get_family(n_local, d, f32=(suf == "f32"), what=3 if (world > 1 or args.force_segments) else 2)
-    per_pass = {k: v[0] / n_probe for k, v in probe.items() if v[1] and k in SLOT_BYTES and slot_bytes(k, d, w, fam_probe) is not None}
-    dominant = max(per_pass, key=per_pass.get) if per_pass else "k_smoother_apply"
-    empty_pair_ms = ctx.profile_calibrate()
-    ctx.profile_read(reset=True)
-    # A timed launch goes out through hipExtLaunchKernelGGL with a start / stop event pair, which costs the stream ~5 us
-    # (measured in round 5: a 20-pass region with every launch stamped 61.7 us per pass, GPU-event time, against 56.8 us in a
-    # 200-pass region stamping every 8th -- the whole "driver protocol is 8 % slower" gap of rounds 2-4; a 55 ms re-warm
-    # changed nothing).  A short region therefore stamps every 5th launch (4 of the driver's 20), a long one every
-    # --event-every-th: <= 2 % of the region either way.
-    sample_every = max(1, args.event_every) if args.steps > 32 else max(1, min(5, args.steps // 4 if args.steps >= 8 else 1))
-    ctx.profile_sample(sample_every)
-    dom_slot = SLOT_INDEX[dominant]
+    if args.full:
+        # which launch slot dominates a pass: measured (events around every launch of a short untimed run), not assumed
+        n_probe = max(3, min(args.warmup, 10))
+        ctx.profile_read(reset=True)
+        ctx.profile_sample(1)
+        ctx.profile_enable(SLOT_MASK)
+        for _ in range(n_probe):
+            step()
+        probe = ctx.profile_read(reset=True)
+        ctx.profile_enable(0)
+        # (only slots whose kernels touch bytes of the contract can be priced against it: the cooperative families' scan slots cannot)
+        fam_probe = ctx.get_family(n_local, d, f32=(suf == "f32"), what=3 if (world > 1 or args.force_segments) else 2)
+        per_pass = {k: v[0] / n_probe for k, v in probe.items() if v[1] and k in SLOT_BYTES and slot_bytes(k, d, w, fam_probe) is not None}
+        dominant = max(per_pass, key=per_pass.get) if per_pass else "k_smoother_apply"
+        empty_pair_ms = ctx.profile_calibrate()
+        ctx.profile_read(reset=True)
+        # A timed launch goes out through hipExtLaunchKernelGGL with a start / stop event pair, which costs the stream ~5 us
+        # (measured in round 5: a 20-pass region with every launch stamped 61.7 us per pass, GPU-event time, against 56.8 us in a
+        # 200-pass region stamping every 8th -- the whole "driver protocol is 8 % slower" gap of rounds 2-4; a 55 ms re-warm
+        # changed nothing).  A short region therefore stamps every 5th launch (4 of the driver's 20), a long one every
+        # --event-every-th: <= 2 % of the region either way.  Without --full no launch is stamped.
+        sample_every = max(1, args.event_every) if args.steps > 32 else max(1, min(5, args.steps // 4 if args.steps >= 8 else 1))
+        ctx.profile_sample(sample_every)
+        dom_slot = SLOT_INDEX[dominant]
     # let the host's CPU-quota window refill after the data generation (a throttled host thread shows up as tens of
     # milliseconds of wall time with an idle GPU) -- and then bring the GPU back to its clocks under load: after half a
     # second of idling a handful of passes (round 4: min(warmup, 10) = 0.45 ms of work) left the 20-step timed region of the
@@ -663,8 +704,9 @@ def main():
         rewarm_batch()
     rewarm_passes = 16 * (1 + n_more)
     rewarm_ms = (time.perf_counter() - rw0) * 1e3
-    ctx.profile_read(reset=True)
-    ctx.profile_enable((1 << dom_slot) if args.event_every > 0 else 0)   # time the dominant slot's launches
+    if args.full:
+        ctx.profile_read(reset=True)
+        ctx.profile_enable((1 << dom_slot) if args.event_every > 0 else 0)   # time the dominant slot's launches
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     barrier()
     torch.cuda.synchronize(dev)
@@ -681,66 +723,75 @@ def main():
     t1 = time.perf_counter()
     gpu_ms = ev0.elapsed_time(ev1)
     elapsed = t1 - t0
-    prof = ctx.profile_read(reset=True)
-    ctx.profile_enable(0)
+    if args.full:
+        prof = ctx.profile_read(reset=True)
+        ctx.profile_enable(0)
     if world > 1:
         tmax = torch.tensor([elapsed, gpu_ms], dtype=torch.float64,
                             device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed, gpu_ms = float(tmax[0].item()), float(tmax[1].item())
 
-    # per-kernel breakdown (separate, untimed loop with events around every launch)
-    ctx.profile_sample(1)
-    ctx.profile_enable(0x7f)
-    n_break = min(args.steps, 50)
-    for _ in range(n_break):
-        step()
-    breakdown = ctx.profile_read(reset=True)
-    ctx.profile_enable(0)
+    # what the last timed pass computed, before any later run overwrites the buffers (the side legs of --full reuse them)
+    if args.dump_outputs:
+        moments = {} if args.path == "fused-ll" else {"filtered_means": fms, "filtered_covs": fPs,
+                                                       "smoothed_means": sms, "smoothed_covs": sPs}
+        dump_outputs(args.dump_outputs, moments, {"log_likelihood": ll_d[:1]}, n_local, DUMP_BYTES // world,
+                     f"_rank{rank}" if world > 1 else "")
 
     ll_val = float(ll_d[0].item())
     status_flags = ctx.status()         # bit 2: float32 calls of this run ran in fp64 arithmetic (dense grid / policy)
     promoted = suf == "f32" and bool(status_flags & 4)
     # the kernel family the timed calls ran on, as the library itself reports it (a promoted float32 call: the fp64 family)
     fam = ctx.get_family(n_local, d, f32=(suf == "f32" and not promoted), what=3 if (world > 1 or args.force_segments) else 2)
-
-    # ---- roofline of the dominant kernel -----------------------------------------------------
-    dom_ms, dom_n = prof[dominant]
-    if not dom_n:                                          # --event-every 0: fall back to the breakdown loop's timing
-        dom_ms, dom_n = breakdown[dominant]
-    # the events are stamped by hipExtLaunchKernelGGL with the dispatch's own start / end timestamps
-    # (the clock rocprofv3's kernel trace reads), so no event-packet overhead is included.  A slot of the row- /
-    # wave-cooperative families can hold several launches per pass (the Kogge-Stone levels sit in the reduce slots);
-    # the two slots that can dominate there, k_filter_apply and k_smoother_apply, are one launch per pass
-    dom_raw_ms = dom_ms / max(dom_n, 1)
-    dom_avg_s = max(dom_raw_ms, 1e-9) * 1e-3
-    dom_bytes = (slot_bytes(dominant, d, w, fam) or 0) * n_local
-    achieved = dom_bytes / dom_avg_s / 1e9 if dom_avg_s > 0 else 0.0
     alg_bytes_step = (7 * d * d + 3 * d + 1) * w
-    # HBM-side bytes per launch of the dominant kernel from the committed PMC profile of this workload
-    traffic, traffic_src, traffic_stale = None, None, None
+    tkey = f"{args.kernel}_{suf}_log2n{args.log2n}"
     default_cfg = (world == 1 and not args.chunk and args.stage < 0 and args.family == 0 and args.path == "lgssm"
                    and args.grid == "baseline" and not args.f32_policy)
-    tkey = f"{args.kernel}_{suf}_log2n{args.log2n}"
-    if default_cfg:
-        traffic, traffic_src, traffic_stale = committed_traffic(tkey, dominant)
-    # every launch slot of the pass against the bytes of the contract it touches itself (two slots within a few per cent of
-    # each other swap the `dominant` role from box to box: read them side by side)
-    slots = {}
-    for sname in SLOT_BYTES:
-        ms_tot, n_l = breakdown.get(sname, (0.0, 0))
-        if not n_l:
-            continue
-        ms_pass = ms_tot / n_break
-        bs = slot_bytes(sname, d, w, fam)
-        ab = bs * n_local if bs is not None else None      # None: the slot's kernels touch no per-step bytes (scans of chain totals)
-        mb = slot_moved_bytes(sname, d, w, fam)
-        tb = committed_traffic(tkey, sname) if default_cfg else (None, None, None)
-        slots[sname] = {"ms_per_pass": ms_pass, "launches_per_pass": n_l / n_break, "alg_bytes": ab,
-                        "moved_bytes_model": mb * n_local if mb is not None else None,
-                        "frac": (ab / (ms_pass * 1e-3) / 1e9 / HBM_PEAK_GBPS if ms_pass > 0 else 0.0) if ab is not None else None,
-                        "traffic": tb[0], "traffic_stale": tb[2]}
-    whole_gbps = alg_bytes_step * n_total * args.steps / (gpu_ms * 1e-3) / 1e9 / world     # per GPU
+
+    if args.full:
+        # per-kernel breakdown (separate, untimed loop with events around every launch)
+        ctx.profile_sample(1)
+        ctx.profile_enable(0x7f)
+        n_break = min(args.steps, 50)
+        for _ in range(n_break):
+            step()
+        breakdown = ctx.profile_read(reset=True)
+        ctx.profile_enable(0)
+
+        # ---- roofline of the dominant kernel -----------------------------------------------------
+        dom_ms, dom_n = prof[dominant]
+        if not dom_n:                                          # --event-every 0: fall back to the breakdown loop's timing
+            dom_ms, dom_n = breakdown[dominant]
+        # the events are stamped by hipExtLaunchKernelGGL with the dispatch's own start / end timestamps
+        # (the clock rocprofv3's kernel trace reads), so no event-packet overhead is included.  A slot of the row- /
+        # wave-cooperative families can hold several launches per pass (the Kogge-Stone levels sit in the reduce slots);
+        # the two slots that can dominate there, k_filter_apply and k_smoother_apply, are one launch per pass
+        dom_raw_ms = dom_ms / max(dom_n, 1)
+        dom_avg_s = max(dom_raw_ms, 1e-9) * 1e-3
+        dom_bytes = (slot_bytes(dominant, d, w, fam) or 0) * n_local
+        achieved = dom_bytes / dom_avg_s / 1e9 if dom_avg_s > 0 else 0.0
+        # HBM-side bytes per launch of the dominant kernel from the committed PMC profile of this workload
+        traffic, traffic_src, traffic_stale = None, None, None
+        if default_cfg:
+            traffic, traffic_src, traffic_stale = committed_traffic(tkey, dominant)
+        # every launch slot of the pass against the bytes of the contract it touches itself (two slots within a few per cent of
+        # each other swap the `dominant` role from box to box: read them side by side)
+        slots = {}
+        for sname in SLOT_BYTES:
+            ms_tot, n_l = breakdown.get(sname, (0.0, 0))
+            if not n_l:
+                continue
+            ms_pass = ms_tot / n_break
+            bs = slot_bytes(sname, d, w, fam)
+            ab = bs * n_local if bs is not None else None      # None: the slot's kernels touch no per-step bytes (scans of chain totals)
+            mb = slot_moved_bytes(sname, d, w, fam)
+            tb = committed_traffic(tkey, sname) if default_cfg else (None, None, None)
+            slots[sname] = {"ms_per_pass": ms_pass, "launches_per_pass": n_l / n_break, "alg_bytes": ab,
+                            "moved_bytes_model": mb * n_local if mb is not None else None,
+                            "frac": (ab / (ms_pass * 1e-3) / 1e9 / HBM_PEAK_GBPS if ms_pass > 0 else 0.0) if ab is not None else None,
+                            "traffic": tb[0], "traffic_stale": tb[2]}
+        whole_gbps = alg_bytes_step * n_total * args.steps / (gpu_ms * 1e-3) / 1e9 / world     # per GPU
 
     out = {
         "metric": "timesteps/sec (filter+smooth+log-lik)",
@@ -764,25 +815,30 @@ def main():
                    f"{world} contiguous time segments, 2 all-gathers of segment totals per pass ("
                    + ("RCCL ncclAllGather issued by libpgps on the context's stream" if use_lib_exchange
                       else f"torch.distributed {args.dist_backend}") + ")"},
-        "roofline": {"bound": "hbm", "kernel": dominant, "kernel_symbol": dominant_symbol(dominant, d, "f64" if promoted else suf, fam),
-                     "kernel_family": fam,
-                     "achieved": achieved, "peak": HBM_PEAK_GBPS,
-                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
-                     "traffic_source": traffic_src, "traffic_stale": traffic_stale, "slots": slots,
-                     "algorithmic_bytes_per_launch": dom_bytes, "avg_launch_ms": dom_avg_s * 1e3,
-                     "launches_timed": dom_n, "launch_sampled_every": sample_every, "empty_event_pair_ms": empty_pair_ms,
-                     "dominant_by": {k: round(v, 6) for k, v in per_pass.items()},
-                     # the whole pass against its algorithmic bytes B_alg = (7d^2+3d+1)w per step, per GPU,
-                     # from the GPU-event time of the timed region
-                     "whole_path_GBps": whole_gbps, "whole_path_frac": whole_gbps / HBM_PEAK_GBPS,
-                     "algorithmic_bytes_per_step": alg_bytes_step,
-                     # from d = 6 the path sits near the vector-FMA ridge, so the same pass is also
-                     # priced against the vector peak with the work-efficient-scan estimate 64 d^3 + 40 d^2 flop per
-                     # step; lower_bound_ms = max(bytes / HBM peak, flops / vector peak) for this rank's steps
-                     "vector_fp": vector_fp(d, suf, n_local, gpu_ms / args.steps, alg_bytes_step)},
-        "whole_path_effective_GBps": alg_bytes_step * n_total * args.steps / elapsed / 1e9,
-        "kernel_ms": {k: (v[0] / v[1] if v[1] else 0.0) for k, v in breakdown.items() if v[1]},
-        "kernel_ms_per_pass": {k: v[0] / n_break for k, v in breakdown.items() if v[1]},
+    }
+    if args.full:
+        out["roofline"] = {
+            "bound": "hbm", "kernel": dominant, "kernel_symbol": dominant_symbol(dominant, d, "f64" if promoted else suf, fam),
+            "kernel_family": fam,
+            "achieved": achieved, "peak": HBM_PEAK_GBPS,
+            "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
+            "traffic_source": traffic_src, "traffic_stale": traffic_stale, "slots": slots,
+            "algorithmic_bytes_per_launch": dom_bytes, "avg_launch_ms": dom_avg_s * 1e3,
+            "launches_timed": dom_n, "launch_sampled_every": sample_every, "empty_event_pair_ms": empty_pair_ms,
+            "dominant_by": {k: round(v, 6) for k, v in per_pass.items()},
+            # the whole pass against its algorithmic bytes B_alg = (7d^2+3d+1)w per step, per GPU,
+            # from the GPU-event time of the timed region
+            "whole_path_GBps": whole_gbps, "whole_path_frac": whole_gbps / HBM_PEAK_GBPS,
+            "algorithmic_bytes_per_step": alg_bytes_step,
+            # from d = 6 the path sits near the vector-FMA ridge, so the same pass is also
+            # priced against the vector peak with the work-efficient-scan estimate 64 d^3 + 40 d^2 flop per
+            # step; lower_bound_ms = max(bytes / HBM peak, flops / vector peak) for this rank's steps
+            "vector_fp": vector_fp(d, suf, n_local, gpu_ms / args.steps, alg_bytes_step)}
+    out["whole_path_effective_GBps"] = alg_bytes_step * n_total * args.steps / elapsed / 1e9
+    if args.full:
+        out["kernel_ms"] = {k: (v[0] / v[1] if v[1] else 0.0) for k, v in breakdown.items() if v[1]}
+        out["kernel_ms_per_pass"] = {k: v[0] / n_break for k, v in breakdown.items() if v[1]}
+    out.update({
         "host_enqueue_ms_per_step": (t_enq - t0) / args.steps * 1e3,
         "gpu_event_ms_per_step": gpu_ms / args.steps,
         "log_likelihood": ll_val,
@@ -791,7 +847,7 @@ def main():
         "chunk": ctx.get_chunk(n_local),
         # lane-chunk kernels (d <= 6): lanes per workgroup, steps per lane, workgroups of the pass that was timed
         "lane_geometry": list(ctx.get_geometry(n_local, d)) if fam in (1, 11) else None,
-    }
+    })
 
     if world > 1 or args.force_segments:
         out["rccl"] = rccl_info
@@ -804,7 +860,8 @@ def main():
                                            "median of 3 rounds of 5 passes, before the communicator is built"}
 
     # ---- the same workload through the fused entry point (ts, ys resident; Fs / Qs never read) ------------
-    if rank == 0 and world == 1 and args.path == "lgssm" and not args.main_only and _backend.nilpotent_form(sde.F) is not None:
+    if (args.full and rank == 0 and world == 1 and args.path == "lgssm" and not args.main_only
+            and _backend.nilpotent_form(sde.F) is not None):
         lam, N1, N2 = _backend.nilpotent_form(sde.F)
         Pinf_h = np.ascontiguousarray(sde.P0, np.float64)
         H_h = np.ascontiguousarray(np.asarray(sde.H, np.float64).reshape(-1))
@@ -887,7 +944,8 @@ def main():
         out["fused_path"] = fused
 
     # ---- general-LTI device path (any kernel, fp64, 2 <= d <= 16): ts, ys in, results out ---------------------
-    if (rank == 0 and world == 1 and args.path == "lgssm" and not args.main_only and dtype_np == np.float64 and 2 <= d <= 16
+    if (args.full and rank == 0 and world == 1 and args.path == "lgssm" and not args.main_only and dtype_np == np.float64
+            and 2 <= d <= 16
             and _backend.nilpotent_form(sde.F) is None):
         F_h = np.ascontiguousarray(sde.F, np.float64)
         Pinf_h = np.ascontiguousarray(sde.P0, np.float64)
@@ -919,7 +977,7 @@ def main():
         out["lti_path"] = lti
 
     # ---- CPU baseline: the oracle's C restatement of the reference's sequential path ----------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import c_oracle
         ssm = (np.asarray(sde.P0), Fs_h.astype(np.float64), Qs_h.astype(np.float64),
                np.asarray(sde.H).reshape(1, -1), np.array([[noise]]))

@@ -1,7 +1,7 @@
 # usage: tools/c2_matrix.sh "<log2n list>" "<stage list>" "<chunk list>" [extra bench args]
 L=${1:-"20 22 24"}; S=${2:-"4"}; C=${3:-"8 16 32"}; shift 3
 for l in $L; do for st in $S; do for ch in $C; do
-python bench.py --log2n $l --stage $st --chunk $ch --steps 30 --warmup 5 --no-cpu-baseline "$@" 2>/dev/null | python -c "
+python bench.py --full --log2n $l --stage $st --chunk $ch --steps 30 --warmup 5 --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import sys,json
 for ln in sys.stdin:
     if ln.startswith('{\"metric\"'):

@@ -1,6 +1,6 @@
 # timing-only variants of rc_apply1 (results are not valid): tools/c5_parts_ab.sh <lib> [<lib> ...]
 for lib in "$@"; do
-PGPS_LIB=$PWD/parallel-gps_amd/pssgp/$lib timeout -k 10 120 python bench.py --kernel c5 --dtype f64 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+PGPS_LIB=$PWD/parallel-gps_amd/pssgp/$lib timeout -k 10 120 python bench.py --full --kernel c5 --dtype f64 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 for ln in sys.stdin:
     if ln.startswith('{'):

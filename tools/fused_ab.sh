@@ -1,6 +1,6 @@
 # compares the side legs of the default bench line between builds: tools/fused_ab.sh <lib> [<lib> ...]
 for lib in "$@"; do
-PGPS_LIB=$PWD/parallel-gps_amd/pssgp/$lib python bench.py --steps 50 --warmup 10 --no-cpu-baseline 2>/dev/null | python -c "
+PGPS_LIB=$PWD/parallel-gps_amd/pssgp/$lib python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 for ln in sys.stdin:
     if ln.startswith('{\"metric\"'):

@@ -10,7 +10,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 run() { # name rows2 args...
   local name=$1 rows=$2; shift 2
-  PGPS_WC_ROWS2=$rows timeout -k 10 280 python3 $R/bench.py "$@" > $O/bench_$name.json 2> $O/bench_$name.err || { echo "bench $name failed"; tail -n 3 $O/bench_$name.err; return 1; }
+  PGPS_WC_ROWS2=$rows timeout -k 10 280 python3 $R/bench.py --full "$@" > $O/bench_$name.json 2> $O/bench_$name.err || { echo "bench $name failed"; tail -n 3 $O/bench_$name.err; return 1; }
   python3 - "$O/bench_$name.json" "$name" <<'PY'
 import json,sys
 r=json.load(open(sys.argv[1])); k=r["kernel_ms_per_pass"]
@@ -28,7 +28,7 @@ run rbf32_d32_2p15_ldstiles 0 --kernel rbf32 --log2n 15 --no-cpu-baseline || exi
 run co2_d18_2p20_tworows 15 --kernel co2 --log2n 20 --no-cpu-baseline --steps 10 --warmup 2 || exit 1
 # per-kernel durations of the CO2 pass
 rm -rf $O/kt_co2
-timeout -k 10 280 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_co2 -- python3 $R/bench.py --kernel co2 --log2n 17 --no-cpu-baseline --steps 50 --warmup 10 > $O/bench_co2_under_rocprof.json 2> /dev/null
+timeout -k 10 280 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_co2 -- python3 $R/bench.py --full --kernel co2 --log2n 17 --no-cpu-baseline --steps 50 --warmup 10 > $O/bench_co2_under_rocprof.json 2> /dev/null
 python3 - $O <<'PY'
 import csv,glob,sys,os
 O=sys.argv[1]

@@ -8,13 +8,13 @@ cd $R
 python tools/fp32_grid_errors.py m32 m52 rbf6 > $O/fp32_grid_errors.txt 2>&1
 for n in 15 20; do
   for pol in 1 0 2; do
-    python bench.py --kernel rbf6 --dtype f32 --log2n $n --grid reference --f32-policy $pol --no-cpu-baseline --main-only --steps 50 --warmup 10 > $O/bench_rbf6_f32_2p${n}_reference_policy$pol.json 2> /dev/null
+    python bench.py --full --kernel rbf6 --dtype f32 --log2n $n --grid reference --f32-policy $pol --no-cpu-baseline --main-only --steps 50 --warmup 10 > $O/bench_rbf6_f32_2p${n}_reference_policy$pol.json 2> /dev/null
   done
 done
-python bench.py --kernel rbf6 --dtype f32 --no-cpu-baseline --main-only > $O/bench_c3_auto.json 2> /dev/null
-python bench.py --kernel rbf6 --dtype f32 --no-cpu-baseline --main-only --f32-policy 1 > $O/bench_c3_native.json 2> /dev/null
-python bench.py --kernel rbf6 --dtype f32 --no-cpu-baseline --main-only > $O/bench_c3_auto_b.json 2> /dev/null
-python bench.py --kernel rbf6 --dtype f32 --no-cpu-baseline --main-only --f32-policy 1 > $O/bench_c3_native_b.json 2> /dev/null
+python bench.py --full --kernel rbf6 --dtype f32 --no-cpu-baseline --main-only > $O/bench_c3_auto.json 2> /dev/null
+python bench.py --full --kernel rbf6 --dtype f32 --no-cpu-baseline --main-only --f32-policy 1 > $O/bench_c3_native.json 2> /dev/null
+python bench.py --full --kernel rbf6 --dtype f32 --no-cpu-baseline --main-only > $O/bench_c3_auto_b.json 2> /dev/null
+python bench.py --full --kernel rbf6 --dtype f32 --no-cpu-baseline --main-only --f32-policy 1 > $O/bench_c3_native_b.json 2> /dev/null
 python3 - $O <<'PY'
 import json,glob,sys,os
 for f in sorted(glob.glob(sys.argv[1]+"/bench_*.json")):

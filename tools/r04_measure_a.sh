@@ -7,10 +7,10 @@ python tools/grad_cost.py > $O/grad_cost.txt 2>&1
 python tools/small_n_latency.py > $O/small_n_latency.txt 2>&1
 for n in 20 21 24; do
   st=100; [ $n = 24 ] && st=30
-  python bench.py --log2n $n --steps $st --warmup 10 --no-cpu-baseline --main-only > $O/bench_c2_2p${n}.json 2>/dev/null
-  python bench.py --log2n $n --steps $st --warmup 10 --no-cpu-baseline --main-only --single-pass 1 > $O/bench_c2_2p${n}_single.json 2>/dev/null
-  python bench.py --log2n $n --steps $st --warmup 10 --no-cpu-baseline --main-only > $O/bench_c2_2p${n}_b.json 2>/dev/null
-  python bench.py --log2n $n --steps $st --warmup 10 --no-cpu-baseline --main-only --single-pass 1 > $O/bench_c2_2p${n}_single_b.json 2>/dev/null
+  python bench.py --full --log2n $n --steps $st --warmup 10 --no-cpu-baseline --main-only > $O/bench_c2_2p${n}.json 2>/dev/null
+  python bench.py --full --log2n $n --steps $st --warmup 10 --no-cpu-baseline --main-only --single-pass 1 > $O/bench_c2_2p${n}_single.json 2>/dev/null
+  python bench.py --full --log2n $n --steps $st --warmup 10 --no-cpu-baseline --main-only > $O/bench_c2_2p${n}_b.json 2>/dev/null
+  python bench.py --full --log2n $n --steps $st --warmup 10 --no-cpu-baseline --main-only --single-pass 1 > $O/bench_c2_2p${n}_single_b.json 2>/dev/null
 done
 python3 - $O <<'PY'
 import json,glob,sys,os

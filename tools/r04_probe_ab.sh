@@ -5,6 +5,6 @@ cd $GRAFT_REPO_ROOT
 for i in 1 2 3 4; do
 for v in "1:0" "0:0" "0:1" "0:2" "0:3"; do
   pol=${v%%:*}; pt=${v#*:}
-  PGPS_PROBE_TEST=$pt python bench.py --kernel rbf6 --dtype f32 --f32-policy $pol --no-cpu-baseline --main-only --steps 100 2>/dev/null | python3 -c "
+  PGPS_PROBE_TEST=$pt python bench.py --full --kernel rbf6 --dtype f32 --f32-policy $pol --no-cpu-baseline --main-only --steps 100 2>/dev/null | python3 -c "
 import sys,json; j=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('round $i policy $pol probe-test $pt: ms %.4f'%j['ms_per_step'], {k: round(v*1e3,1) for k,v in j['kernel_ms_per_pass'].items()})"
 done; done

@@ -9,11 +9,11 @@ cd $R
 bash tools/pmc.sh pmc_c2_r05 && python3 tools/pmc_traffic.py gpurun_out/pmc_c2_r05 matern32_f64_log2n20 $R/profiles/r05_traffic.json && cp gpurun_out/pmc_c2_r05/summary.txt $O/c2_pmc_summary.txt
 bash tools/pmc.sh pmc_c2f_r05 --path fused && python3 tools/pmc_traffic.py gpurun_out/pmc_c2f_r05 matern32_f64_log2n20 $R/profiles/r05_traffic.json 2.0 k_pkfs_resident=fused_path && cp gpurun_out/pmc_c2f_r05/summary.txt $O/c2_fused_pmc_summary.txt
 cp $R/profiles/r05_traffic.json $O/r05_traffic.json
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_c2_driver_protocol.json 2> $O/bench_c2.err
-python bench.py > $O/bench_c2.json 2>> $O/bench_c2.err
-python bench.py --resident 0 --no-cpu-baseline > $O/bench_c2_three_launches.json 2>> $O/bench_c2.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_c2_driver_protocol.json 2> $O/bench_c2.err
+python bench.py --full > $O/bench_c2.json 2>> $O/bench_c2.err
+python bench.py --full --resident 0 --no-cpu-baseline > $O/bench_c2_three_launches.json 2>> $O/bench_c2.err
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_c2 -- python3 $R/bench.py --no-cpu-baseline --steps 50 --warmup 10 > $O/bench_c2_under_rocprof.json 2> /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_c2 -- python3 $R/bench.py --full --no-cpu-baseline --steps 50 --warmup 10 > $O/bench_c2_under_rocprof.json 2> /dev/null
 python3 - "$O/kt_c2" "$O/c2_kernel_stats.txt" <<'PY'
 import csv,glob,sys
 f=glob.glob(sys.argv[1]+"/**/*kernel_stats.csv", recursive=True)[0]

@@ -1,7 +1,7 @@
 # A/B of libpgps builds on fp64 RBF models of order 8..10 (row-cooperative kernels): tools/rc_occ_ab.sh <lib> [<lib> ...]
 for k in rbf8 rbf9 rbf10; do
 for lib in "$@"; do
-PGPS_LIB=$PWD/parallel-gps_amd/pssgp/$lib timeout -k 10 120 python bench.py --kernel $k --dtype f64 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+PGPS_LIB=$PWD/parallel-gps_amd/pssgp/$lib timeout -k 10 120 python bench.py --full --kernel $k --dtype f64 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 for ln in sys.stdin:
     if ln.startswith('{'):
