@@ -91,6 +91,15 @@ int pgps_set_shortcut(pgps_ctx* ctx, int on);
 /* Diagnostics: cycle stamps of the last resident launch made under mode 2: out = (n_blocks, 16) long long (host), at most
  * max_blocks rows copied; out may be NULL to ask for n_blocks only. */
 int pgps_resident_stamps(pgps_ctx* ctx, long long* out, int max_blocks, int* n_blocks);
+/* Diagnostics: a deterministic start skew for the resident launch's hand-offs (the tests' view of a shared GPU).  Armed
+ * (tile 0..255), every following resident launch makes workgroup `tile` wait `microseconds` (0..10000) of the wall clock
+ * before it publishes its phase-1 total (phase 1: the filtering total) or its phase-2 total (phase 2: the smoothing total
+ * and log-likelihood partial); the launch's spine records are filled with NaN first, so a record read before it is
+ * published shows.  pgps_resident_stamps then also returns wall-clock stamps (device wall clock, constant rate) in
+ * slots 10 .. 13 of every row: 10 / 11 = that workgroup's phase-1 / phase-2 publish, 12 = the start of the armed
+ * workgroup's wait, 13 = its length in wall-clock ticks (both in the armed workgroup's row); the cycle stamps of slots
+ * 0 .. 9 only under pgps_set_resident(ctx, 2).  tile = -1 disarms it (the state after pgps_create). */
+int pgps_debug_resident_delay(pgps_ctx* ctx, int tile, int phase, int microseconds);
 /* Kernel family: 0 = automatic (lane-chunk for d <= 4 and for fp32 up to PGPS_MAX_DIM_LANE; row-cooperative for
  * fp64 with 5 <= d <= 16 and fp32 with 7 <= d <= 16, segments use it above d = 6; quad-cooperative for whole fp32
  * series at d = 8 and, up to 3 * 2^17 and from 3 * 2^19 steps, at d = 6; wave-cooperative otherwise, d <= 32),

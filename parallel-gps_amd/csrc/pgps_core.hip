@@ -196,6 +196,25 @@ extern "C" int pgps_resident_stamps(pgps_ctx* ctx, long long* out, int max_block
     return PGPS_OK;
 }
 
+// diagnostics: start skew of the resident launch (pgps_resident.hip.h, res_skew)
+extern "C" int pgps_debug_resident_delay(pgps_ctx* ctx, int tile, int phase, int microseconds) {
+    if (!ctx || tile < -1 || tile > 255 || (tile >= 0 && (phase < 1 || phase > 2 || microseconds < 0 || microseconds > 10000)))
+        return PGPS_E_INVALID;
+    if (tile < 0) {
+        ctx->res_delay_tile = -1;
+        ctx->res_delay_phase = 0;
+        ctx->res_delay_ticks = 0;
+        return PGPS_OK;
+    }
+    int khz = 0;
+    HIPCHK(ctx, hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, ctx->device));
+    if (khz <= 0) return PGPS_E_HIP;
+    ctx->res_delay_tile = tile;
+    ctx->res_delay_phase = phase;
+    ctx->res_delay_ticks = (long long)microseconds * khz / 1000;
+    return PGPS_OK;
+}
+
 extern "C" int pgps_set_family(pgps_ctx* ctx, int family) {
     if (!ctx || family < 0 || family > 4) return PGPS_E_INVALID;
     ctx->family = family;
@@ -447,7 +466,9 @@ bool resident_fits(const pgps_ctx* ctx, long N, int d, bool f32) {
     const bool own_chunk = ctx->resident > 0 && (ctx->chunk == 8 || ctx->chunk == 16);
     if ((ctx->chunk > 0 && !own_chunk) || ctx->block != 0 || ctx->stage_g >= 0 || ctx->single_pass > 0 || ctx->dma > 0) return false;
     if (ctx->family != 0 && ctx->family != 1) return false;
-    if (N > (long)kBlock * (own_chunk ? ctx->chunk : kResLc) * ctx->n_cu) return false;
+    // one workgroup per CU, and at most kResMaxBlocks of them (the hand-off flags, one record per lane in the general fold)
+    const long max_blocks = ctx->n_cu < kResMaxBlocks ? ctx->n_cu : kResMaxBlocks;
+    if (N > (long)kBlock * (own_chunk ? ctx->chunk : kResLc) * max_blocks) return false;
     // not while the stream is being captured: the launch's barrier set and hand-off epoch are chosen per launch on the host,
     // and a replayed graph would present the same ones again (counters already at their targets, flags already equal)
     if (!(ctx->resident > 0 || N >= kResAutoMin)) return false;         // (before the query below: short series never pay for it)

@@ -35,6 +35,9 @@ struct pgps_ctx {
     unsigned res_epoch = 0;             // launches of the resident kernel so far: picks the barrier's counter set
     DevBuf res_stamps;                  // diagnostics: (workgroups, 16) cycle stamps of the last resident launch
     int res_stamp_blocks = 0;
+    int res_delay_tile = -1;            // diagnostics (pgps_debug_resident_delay): the workgroup that waits before it publishes, -1 = none
+    int res_delay_phase = 0;            // ... its phase-1 (1) or phase-2 (2) total
+    long long res_delay_ticks = 0;      // ... for this many wall-clock ticks
     int family = 0;                     // 0 = auto (lane-chunk d <= 6; row-cooperative fp64 d <= 16; else wave-cooperative), 1 = lane, 2 = wave, 3 = row
     std::string hip_err;
     DevBuf ws;                          // scratch of the scan kernels
@@ -210,17 +213,29 @@ template <typename T>
 struct ResArgs {
     ScanArgs<T> s;          // N, nblocks, model, series, outputs, spine / sspine / llpart, status, ll
     GpModel<T> m;           // fused form: the Matern model (F = -lam I + N) and the time stamps
-    int* bar;               // this launch's 8 counter shards (32 ints apart), zero on entry
-    int* bar_next;          // the next launch's: zeroed by this one
+    int* bar;               // this launch's barrier 1: 8 counter shards (32 ints apart) of first arrivals, zero on entry
+    int* bar2;              // ... barrier 2: 8 shards of second arrivals (bar + kResBarSet / 2)
+    int* bar_next;          // the next launch's set (both barriers): zeroed by this one
     int* flags1;            // per workgroup: `epoch` once its filtering total is published (the neighbour hand-off)
     int* flags2;            // ... once its smoothing total and log-likelihood partial are
     int epoch;              // this launch's (never 0)
     long long* stamps;      // diagnostics (pgps_set_resident(ctx, 2)): (nblocks, 16) cycle stamps, else null
+    // diagnostics (pgps_debug_resident_delay): start skew.  Workgroup `delay_tile` (-1: none) waits `delay_ticks` wall-clock
+    // ticks before it publishes its phase-`delay_phase` total; wstamps (null unless armed) = the stamps buffer, whose slots
+    // 10 .. 13 then take wall-clock stamps (pgps.h)
+    int delay_tile;
+    int delay_phase;
+    long long delay_ticks;
+    long long* wstamps;
 };
 constexpr int kResLc = 16;                  // steps per lane: the chunk lives in registers
 constexpr int kStatusBytes = 8192;          // the context's status buffer: word 0 flags, 16.. tickets, 512.. the resident kernel's barrier counters
-constexpr int kResBarWord = 512;            // two sets of 8 shards x 32 ints
-constexpr int kResFlagWord = 1024;          // two arrays of 256 per-workgroup hand-off flags (words 1024 .. 1535)
+constexpr int kResBarWord = 512;            // two sets (alternating launches) of two barriers x 8 shards x 32 ints (words 512 .. 1535)
+constexpr int kResBarSet = 2 * 8 * 32;
+constexpr int kResFlagWord = 1536;          // two arrays of 256 per-workgroup hand-off flags (words 1536 .. 2047)
+constexpr int kResMaxBlocks = 256;          // workgroups of one resident launch: the flag arrays, one record per lane in the general fold
+static_assert(kResBarWord + 2 * kResBarSet <= kResFlagWord, "barrier counters overlap the hand-off flags");
+static_assert((kResFlagWord + 2 * kResMaxBlocks) * 4 <= kStatusBytes, "hand-off flags outside the status buffer");
 // does a whole-series filter + smoother call of N steps at dimension d (fp64 when !f32) take the resident launch?
 bool resident_fits(const pgps_ctx* ctx, long N, int d, bool f32);
 template <typename T, int D>

@@ -14,12 +14,14 @@ int launch_resident(pgps_ctx* ctx, ResArgs<T> ra, bool fused, bool smooth) {
     ScanArgs<T>& a = ra.s;
     // steps per lane: 16 (4096 per workgroup) -- or 8 where the whole series then still fits the chip: twice the workgroups
     // for series of up to 2048 steps per CU, which at 16 would leave half of the CUs idle (2^19 steps: 39 -> 30 us)
+    const int max_blocks = ctx->n_cu < kResMaxBlocks ? ctx->n_cu : kResMaxBlocks;
     int lc = kResLc;
     if (ctx->resident > 0 && (ctx->chunk == 8 || ctx->chunk == 16)) lc = ctx->chunk;
-    else if (a.N <= (long)kBlock * 8 * ctx->n_cu) lc = 8;
+    else if (a.N <= (long)kBlock * 8 * max_blocks) lc = 8;
     a.Lc = lc;
     a.nblocks = (int)((a.N + (long)kBlock * lc - 1) / ((long)kBlock * lc));
-    if (a.nblocks < 1 || a.nblocks > ctx->n_cu) return PGPS_E_INVALID;      // every workgroup must be resident
+    // every workgroup must be resident, and the hand-off flags and the general fold hold kResMaxBlocks workgroups
+    if (a.nblocks < 1 || a.nblocks > max_blocks) return PGPS_E_INVALID;
     a.nlanes = (long)a.nblocks * kBlock;
     a.seg_first = 1;
     a.seg_last = 1;
@@ -39,23 +41,39 @@ int launch_resident(pgps_ctx* ctx, ResArgs<T> ra, bool fused, bool smooth) {
     a.llpart = (double*)(base + o_ll);
     a.status = ctx->status_word;
     const unsigned e = ctx->res_epoch++;
-    ra.bar = ctx->status_word + kResBarWord + (e & 1u) * 256;
-    ra.bar_next = ctx->status_word + kResBarWord + ((e + 1u) & 1u) * 256;
+    ra.bar = ctx->status_word + kResBarWord + (e & 1u) * kResBarSet;
+    ra.bar2 = ra.bar + kResBarSet / 2;
+    ra.bar_next = ctx->status_word + kResBarWord + ((e + 1u) & 1u) * kResBarSet;
     ra.flags1 = ctx->status_word + kResFlagWord;
-    ra.flags2 = ctx->status_word + kResFlagWord + 256;
+    ra.flags2 = ctx->status_word + kResFlagWord + kResMaxBlocks;
     ra.epoch = (int)(e % 0x7ffffffeu) + 1;           // compared for equality: a stale flag of any earlier launch never matches
-    static_assert(kResFlagWord * 4 + 2 * 256 * 4 <= kStatusBytes, "hand-off flags outside the status buffer");
     ra.stamps = nullptr;
-    if (ctx->resident == 2) {
+    ra.wstamps = nullptr;
+    ra.delay_tile = -1;
+    ra.delay_phase = 0;
+    ra.delay_ticks = 0;
+    const bool skew = ctx->res_delay_tile >= 0;        // the start-skew hook (pgps_debug_resident_delay): diagnostics only
+    if (ctx->resident == 2 || skew) {
         rc = ensure(ctx, ctx->res_stamps, nb * 16 * sizeof(long long));
         if (rc) return rc;
-        ra.stamps = (long long*)ctx->res_stamps.p;
+        if (ctx->resident == 2) ra.stamps = (long long*)ctx->res_stamps.p;
         ctx->res_stamp_blocks = a.nblocks;
+    }
+    if (skew) {
+        // every record a workgroup could read before it is published is NaN: a stale read cannot match by luck
+        HIPCHK(ctx, hipMemsetAsync(ctx->res_stamps.p, 0, nb * 16 * sizeof(long long), ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(base, 0xFF, off, ctx->stream));
+        ra.wstamps = (long long*)ctx->res_stamps.p;
+        ra.delay_tile = ctx->res_delay_tile;
+        ra.delay_phase = ctx->res_delay_phase;
+        ra.delay_ticks = ctx->res_delay_ticks;
     }
     const dim3 grid(a.nblocks), block(kBlock);
     auto go = [&](auto lcv, auto fusedv, auto smoothv) {
-        timed_launch(ctx, PGPS_K_RESIDENT, k_pkfs_resident<T, D, decltype(lcv)::value, decltype(fusedv)::value, decltype(smoothv)::value>,
-                     grid, block, 0, ra);
+        constexpr int L = decltype(lcv)::value;
+        constexpr bool FU = decltype(fusedv)::value, SM = decltype(smoothv)::value;
+        if (skew) timed_launch(ctx, PGPS_K_RESIDENT, k_pkfs_resident<T, D, L, FU, SM, true>, grid, block, 0, ra);
+        else timed_launch(ctx, PGPS_K_RESIDENT, k_pkfs_resident<T, D, L, FU, SM, false>, grid, block, 0, ra);
     };
     auto pick = [&](auto lcv) {
         if (fused) { if (smooth) go(lcv, std::true_type{}, std::true_type{}); else go(lcv, std::true_type{}, std::false_type{}); }

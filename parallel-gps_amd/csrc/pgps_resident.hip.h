@@ -28,13 +28,18 @@
 // with sc1 loads in place of the acquire): one lane stores the record with agent-scope atomic (write-through) stores,
 // drains them, adds one arrival to the counter shard of its tile; eight lanes poll one shard each with relaxed
 // agent-scope loads; the records are read with agent-scope atomic loads only.  Every spin is bounded (status bit 1).
-// The two barriers of a launch count on ONE set of eight shards (targets n and 2 n); two sets alternate between
-// launches and every launch zeroes the set of the next one, so nothing is memset in front of a launch and a launch that
-// gave up leaves no debt.
+// Each of the two barriers of a launch counts on eight shards of its OWN (target n each): a workgroup that runs ahead --
+// workgroup 0 never waits in phase 2, nor does one whose left neighbour's total has forgotten -- arrives at barrier 2
+// while others are still in phase 1, and on shared counters its second arrival could stand in for a first arrival that
+// has not happened (a record read before it was published).  Two sets of both alternate between launches and every
+// launch zeroes the set of the next one, so nothing is memset in front of a launch and a launch that gave up leaves no
+// debt.
 //
 // Ragged series: steps at or beyond N are padded ON LOAD with the scan's identity step (F = I, Q = 0, y = NaN: a pure
-// predict that changes nothing), their smoothing elements are forced to the identity, the element of step N - 1 is the
-// reference's last element (0, m, P) (parallel.py:155-156), and stores beyond N are predicated off -- one code path.
+// predict that changes nothing), the element of step N - 1 is the reference's last element (0, m, P) (parallel.py:155-156)
+// with E exactly zero, the padded steps' elements (about the identity, from smth_element on F = I, Q = 0) lie to its right
+// and reach nothing as long as they are finite (tests/test_gpu_resident_skew.py: near-singular filtered P before the
+// padding), and stores beyond N are predicated off -- one code path.
 #pragma once
 
 #include <type_traits>
@@ -79,6 +84,25 @@ template <> struct ResForget<float> { static constexpr float kA = 0x1p-60f; };
     do {                                                                                              \
         if (ra.stamps && threadIdx.x == 0) ra.stamps[(long)blockIdx.x * 16 + (IDX)] = __builtin_readcyclecounter(); \
     } while (0)
+
+// Diagnostics (pgps_debug_resident_delay): a deterministic start skew.  The armed workgroup's publishing lane waits
+// `ticks` of the wall clock (constant rate, one clock for the whole chip) before it publishes the total of the armed phase,
+// and wall-clock stamps go to slots 10 .. 13 of the stamps rows: 10 / 11 = the workgroup's phase-1 / phase-2 publish
+// (drained, just before its arrival), 12 = the start of the wait, 13 = its length in ticks.  Only the SKEW instantiations
+// of the kernel carry it (launched while the hook is armed): the default ones hold none of its code.
+template <typename T>
+__device__ __forceinline__ void res_skew(const ResArgs<T>& ra, int tile, int phase) {
+    if (tile == ra.delay_tile && phase == ra.delay_phase) {
+        const long long t0 = wall_clock64();
+        ra.wstamps[(long)tile * 16 + 12] = t0;
+        ra.wstamps[(long)tile * 16 + 13] = ra.delay_ticks;
+        while (wall_clock64() - t0 < ra.delay_ticks) __builtin_amdgcn_s_sleep(8);
+    }
+}
+template <typename T>
+__device__ __forceinline__ void res_wstamp(const ResArgs<T>& ra, int tile, int slot) {
+    if (ra.wstamps) ra.wstamps[(long)tile * 16 + slot] = wall_clock64();
+}
 
 // one 16-byte piece of an identity-step record: kind 0 = F (identity matrix), 1 = Q (zero)
 template <typename T, int D>
@@ -158,21 +182,17 @@ __device__ __forceinline__ void res_drain_m(char* __restrict__ g /*wave-uniform*
     }
 }
 
-// one arrival of this workgroup at a grid-wide barrier and the wait for `rounds` x (every workgroup's arrival).
-// The caller's lane 0 has drained the stores it publishes (s_waitcnt vmcnt(0)) before this is called.
-__device__ __forceinline__ void res_wait_all(int* bar, int nblocks, int rounds, int* status) {
+// the wait for every workgroup's arrival at the grid-wide barrier whose counters `bar` holds (one arrival per workgroup).
+// The arriving lane has drained the stores it publishes (s_waitcnt vmcnt(0)) before it arrives.
+__device__ __forceinline__ void res_wait_all(int* bar, int nblocks, int* status) {
     if (threadIdx.x < 8) {
-        const int want = rounds * ((nblocks - (int)threadIdx.x + 7) / 8);       // tiles whose index is threadIdx.x mod 8
+        const int want = (nblocks - (int)threadIdx.x + 7) / 8;       // tiles whose index is threadIdx.x mod 8
         if (want > 0) wait_flag(bar + threadIdx.x * 32, want, status);
     }
     __syncthreads();
 }
 __device__ __forceinline__ void res_arrive(int* bar, int tile) {
     __hip_atomic_fetch_add(bar + (tile & 7) * 32, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void res_grid_barrier(int* bar, int tile, int nblocks, int rounds, int* status) {
-    if (threadIdx.x == 0) res_arrive(bar, tile);
-    res_wait_all(bar, nblocks, rounds, status);
 }
 
 // The neighbour hand-off (round 5, with the forgetting shortcut): a workgroup that can take its carry from ONE neighbour's
@@ -441,7 +461,7 @@ struct ResLaneValues {
 
 // SMOOTH = false: the filter alone (pkf: filtered moments and / or the log-likelihood) -- phases 1 and 2 without the smoothing
 // elements, one hand-off; the series still stays on chip between the reduce and the Kalman pass, i.e. Fs, Qs, ys are read once.
-template <typename T, int D, int LC, bool FUSED, bool SMOOTH = true>
+template <typename T, int D, int LC, bool FUSED, bool SMOOTH = true, bool SKEW = false>
 __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
     using CFG = ResCfg<T, D, LC>;
     using GF = typename CFG::GF;
@@ -467,7 +487,7 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
     T* myrec = reinterpret_cast<T*>(myslot);
 
     PGPS_RSTAMP(0);
-    if (tile == 0 && threadIdx.x < 8) ra.bar_next[threadIdx.x * 32] = 0;
+    if (tile == 0 && threadIdx.x < 16) ra.bar_next[threadIdx.x * 32] = 0;        // both barriers' shards of the next launch
 
     const long N = a.N;
     const long gt = (long)tile * kBlock + threadIdx.x;
@@ -601,10 +621,12 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
         if (threadIdx.x == kWaves - 1) {            // the lane the forward scan leaves the workgroup's total in
             T v[NF];
             pack(total, v);
+            if constexpr (SKEW) res_skew(ra, tile, 1);
 #pragma unroll
             for (int i = 0; i < NF; ++i) pub_store(a.spine + (long)tile * NF + i, v[i]);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             pub_store(ra.flags1 + tile, ra.epoch);
+            if constexpr (SKEW) res_wstamp(ra, tile, 10);
             res_arrive(ra.bar, tile);
         }
     }
@@ -624,7 +646,7 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
             if (threadIdx.x == 0) res_wait_epoch(ra.flags1 + tile - 1, ra.epoch, a.status);
             __syncthreads();
         } else {
-            res_wait_all(ra.bar, a.nblocks, 1, a.status);
+            res_wait_all(ra.bar, a.nblocks, a.status);
             waited_all = true;
         }
         // The forgetting shortcut.  The carry into this tile is the prefix T_0 (x) ... (x) T_{tile-1} applied to the prior; in
@@ -652,7 +674,7 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
 #pragma unroll
             for (int i = 0; i < SYM; ++i) s.P[i] = nb.C[i];
         } else {
-            if (!waited_all) res_wait_all(ra.bar, a.nblocks, 1, a.status);     // every total to the left is needed
+            if (!waited_all) res_wait_all(ra.bar, a.nblocks, a.status);     // every total to the left is needed
             FE mine, left;
             filt_identity(mine);
             if ((int)threadIdx.x < tile) {
@@ -782,12 +804,14 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
         const double v = ll.value();
         const double t = block_sum_double(v, lds_ll);
         if (threadIdx.x == 0) {
+            if constexpr (SKEW) res_skew(ra, tile, 2);
             pub_store(a.llpart + tile, t);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            res_arrive(ra.bar, tile);
+            if constexpr (SKEW) res_wstamp(ra, tile, 11);
+            res_arrive(ra.bar2, tile);
         }
         if (tile == 0 && a.ll != nullptr) {
-            res_wait_all(ra.bar, a.nblocks, 2, a.status);
+            res_wait_all(ra.bar2, a.nblocks, a.status);
             double w = 0.0;
             for (int b = threadIdx.x; b < a.nblocks; b += kBlock) w += pub_load(a.llpart + b);
             const double tt = block_sum_double(w, lds_ll);
@@ -826,12 +850,14 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
         if (threadIdx.x == 0) {                     // (the backward scan leaves its total in lane 0)
             T vv[NS];
             pack(stotal, vv);
+            if constexpr (SKEW) res_skew(ra, tile, 2);
 #pragma unroll
             for (int i = 0; i < NS; ++i) pub_store(a.sspine + (long)tile * NS + i, vv[i]);
             pub_store(a.llpart + tile, t);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             pub_store(ra.flags2 + tile, ra.epoch);
-            res_arrive(ra.bar, tile);
+            if constexpr (SKEW) res_wstamp(ra, tile, 11);
+            res_arrive(ra.bar2, tile);
         }
     }
 
@@ -848,7 +874,7 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
             if (threadIdx.x == 0) res_wait_epoch(ra.flags2 + tile + 1, ra.epoch, a.status);
             __syncthreads();
         } else {
-            res_wait_all(ra.bar, a.nblocks, 2, a.status);
+            res_wait_all(ra.bar2, a.nblocks, a.status);
             waited_all = true;
         }
         // the same shortcut backwards: a smoothing total whose E vanishes (the product of 4096 smoother gains) hands the tile
@@ -870,7 +896,7 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
 #pragma unroll
             for (int i = 0; i < SYM; ++i) s.P[i] = nb.L[i];
         } else {
-            if (!waited_all) { res_wait_all(ra.bar, a.nblocks, 2, a.status); waited_all = true; }
+            if (!waited_all) { res_wait_all(ra.bar2, a.nblocks, a.status); waited_all = true; }
             SE mine, right;
             smth_identity(mine);
             const int b = tile + 1 + (int)threadIdx.x;
@@ -890,7 +916,7 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
     smth_apply(sexcl, s);
     PGPS_RSTAMP(8);
     if (tile == 0 && a.ll != nullptr) {
-        if (!waited_all) res_wait_all(ra.bar, a.nblocks, 2, a.status);         // every workgroup's partial is out
+        if (!waited_all) res_wait_all(ra.bar2, a.nblocks, a.status);         // every workgroup's partial is out
         double v = 0.0;
         for (int b = threadIdx.x; b < a.nblocks; b += kBlock) v += pub_load(a.llpart + b);
         const double t = block_sum_double(v, lds_ll);

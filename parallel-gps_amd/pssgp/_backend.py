@@ -55,6 +55,8 @@ def _declare(lib):
     if hasattr(lib, "pgps_set_resident"):       # (absent from libraries built before round 5: A/B runs load those)
         lib.pgps_set_resident.argtypes = [P, c_int]
         lib.pgps_resident_stamps.argtypes = [P, P, c_int, ctypes.POINTER(c_int)]
+    if hasattr(lib, "pgps_debug_resident_delay"):
+        lib.pgps_debug_resident_delay.argtypes = [P, c_int, c_int, c_int]
     if hasattr(lib, "pgps_set_shortcut"):
         lib.pgps_set_shortcut.argtypes = [P, c_int]
     if hasattr(lib, "pgps_set_rc_scan"):
@@ -215,12 +217,20 @@ class Context:
             check(self, self.lib.pgps_set_shortcut(self.handle, int(on)), "pgps_set_shortcut")
 
     def resident_stamps(self):
-        """(workgroups, 16) cycle stamps of the last resident launch made under set_resident(2) (diagnostics)."""
+        """(workgroups, 16) cycle stamps of the last resident launch made under set_resident(2), and wall-clock stamps in
+        slots 10 .. 13 when debug_resident_delay is armed (diagnostics)."""
         n = c_int(0)
         check(self, self.lib.pgps_resident_stamps(self.handle, None, 0, ctypes.byref(n)), "pgps_resident_stamps")
         out = np.zeros((max(n.value, 1), 16), np.int64)
         check(self, self.lib.pgps_resident_stamps(self.handle, _ptr(out), n.value, ctypes.byref(n)), "pgps_resident_stamps")
         return out[:n.value]
+
+    def debug_resident_delay(self, tile, phase=1, microseconds=200):
+        """Diagnostics: workgroup `tile` of every following resident launch waits `microseconds` before it publishes its
+        phase-1 / phase-2 total (spine records NaN-filled first); wall-clock stamps in slots 10 .. 13 of resident_stamps().
+        tile = -1 disarms it (pgps_debug_resident_delay)."""
+        check(self, self.lib.pgps_debug_resident_delay(self.handle, int(tile), int(phase), int(microseconds)),
+              "pgps_debug_resident_delay")
 
     def set_one_launch(self, max_steps):
         """Fused calls of short series in ONE launch up to max_steps steps: -1 automatic (2048 steps: kOneLaunchAuto), 0 never."""
