@@ -91,6 +91,10 @@ int pgps_set_shortcut(pgps_ctx* ctx, int on);
 /* Diagnostics: cycle stamps of the last resident launch made under mode 2: out = (n_blocks, 16) long long (host), at most
  * max_blocks rows copied; out may be NULL to ask for n_blocks only. */
 int pgps_resident_stamps(pgps_ctx* ctx, long long* out, int max_blocks, int* n_blocks);
+/* Diagnostics: per-wave stamps of the same launch (mode 2): out = (n_blocks, 8) long long, entry k * 4 + wave = the cycle
+ * count at which that wave ended its reduce (k = 0) / its Kalman pass (k = 1); slots 1 and 5 of pgps_resident_stamps are
+ * wave 0's, after it has waited for the slower waves at a barrier. */
+int pgps_resident_wave_stamps(pgps_ctx* ctx, long long* out, int max_blocks, int* n_blocks);
 /* Diagnostics: a deterministic start skew for the resident launch's hand-offs (the tests' view of a shared GPU).  Armed
  * (tile 0..255), every following resident launch makes workgroup `tile` wait `microseconds` (0..10000) of the wall clock
  * before it publishes its phase-1 total (phase 1: the filtering total) or its phase-2 total (phase 2: the smoothing total

@@ -196,6 +196,19 @@ extern "C" int pgps_resident_stamps(pgps_ctx* ctx, long long* out, int max_block
     return PGPS_OK;
 }
 
+// diagnostics: every wave's end of the reduce and of the Kalman pass in the last resident launch made with
+// pgps_set_resident(ctx, 2): (workgroups, 8) long long, [k * 4 + wave], after the (workgroups, 16) table on the device
+extern "C" int pgps_resident_wave_stamps(pgps_ctx* ctx, long long* out, int max_blocks, int* n_blocks) {
+    if (!ctx || !n_blocks) return PGPS_E_INVALID;
+    *n_blocks = ctx->res_stamp_blocks;
+    if (!out || max_blocks <= 0 || !ctx->res_stamps.p) return PGPS_OK;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    const int n = ctx->res_stamp_blocks < max_blocks ? ctx->res_stamp_blocks : max_blocks;
+    const long long* waves = (const long long*)ctx->res_stamps.p + (size_t)ctx->res_stamp_blocks * 16;
+    HIPCHK(ctx, hipMemcpy(out, waves, (size_t)n * 8 * sizeof(long long), hipMemcpyDeviceToHost));
+    return PGPS_OK;
+}
+
 // diagnostics: start skew of the resident launch (pgps_resident.hip.h, res_skew)
 extern "C" int pgps_debug_resident_delay(pgps_ctx* ctx, int tile, int phase, int microseconds) {
     if (!ctx || tile < -1 || tile > 255 || (tile >= 0 && (phase < 1 || phase > 2 || microseconds < 0 || microseconds > 10000)))

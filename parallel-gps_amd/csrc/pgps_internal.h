@@ -217,7 +217,7 @@ struct ResArgs {
     int* bar2;              // ... barrier 2: 8 shards of second arrivals (bar + kResBarSet / 2)
     int* bar_next;          // the next launch's set (both barriers): zeroed by this one
     int* flags1;            // per workgroup: `epoch` once its filtering total is published (the neighbour hand-off)
-    int* flags2;            // ... once its smoothing total and log-likelihood partial are
+    int* flags2;            // ... once its smoothing total is (its log-likelihood partial follows, before its arrival at bar2)
     int epoch;              // this launch's (never 0)
     long long* stamps;      // diagnostics (pgps_set_resident(ctx, 2)): (nblocks, 16) cycle stamps, else null
     // diagnostics (pgps_debug_resident_delay): start skew.  Workgroup `delay_tile` (-1: none) waits `delay_ticks` wall-clock

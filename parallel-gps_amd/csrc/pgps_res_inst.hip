@@ -54,7 +54,8 @@ int launch_resident(pgps_ctx* ctx, ResArgs<T> ra, bool fused, bool smooth) {
     ra.delay_ticks = 0;
     const bool skew = ctx->res_delay_tile >= 0;        // the start-skew hook (pgps_debug_resident_delay): diagnostics only
     if (ctx->resident == 2 || skew) {
-        rc = ensure(ctx, ctx->res_stamps, nb * 16 * sizeof(long long));
+        // (nblocks, 16) workgroup stamps, then (nblocks, 8) per-wave stamps (pgps_resident_wave_stamps)
+        rc = ensure(ctx, ctx->res_stamps, nb * (16 + 8) * sizeof(long long));
         if (rc) return rc;
         if (ctx->resident == 2) ra.stamps = (long long*)ctx->res_stamps.p;
         ctx->res_stamp_blocks = a.nblocks;

@@ -10,12 +10,13 @@
 //
 //   phase 1   stream the lane's LC steps in (coalesced, transposed through the wave's LDS slots): F stays in
 //             registers, Q stays in the lane's LDS slot, y in registers; lane-serial filt_extend -> lane aggregate;
-//             workgroup scan; the workgroup's total is published (write-through stores)
+//             workgroup scan; the workgroup's total is published (write-through stores) the moment the scan has it
 //   barrier 1 grid-wide (every workgroup resident: grid <= CUs, one workgroup per CU by its LDS footprint)
 //   phase 2   fold the totals to the left, Kalman pass over the kept F, Q, y: fms, fPs out (through the slots Q has
 //             left, drained coalesced), log-likelihood, and the smoothing element (E, g, L) of every step
 //             (parallel.py:159-166) IN PLACE of the step's inputs: E, g in the registers F and y have left, L in
-//             the slot; lane aggregate of the elements, workgroup suffix scan, total published
+//             the slot; lane aggregate of the elements, workgroup suffix scan, total published; then the workgroup's
+//             log-likelihood partial, while the right neighbour's total is still on its way
 //   barrier 2
 //   phase 3   fold the totals to the right, lane-serial smoothing-operator pass (parallel.py:176-184) backwards over
 //             the kept elements: sms, sPs out through the slots
@@ -83,6 +84,13 @@ template <> struct ResForget<float> { static constexpr float kA = 0x1p-60f; };
 #define PGPS_RSTAMP(IDX)                                                                              \
     do {                                                                                              \
         if (ra.stamps && threadIdx.x == 0) ra.stamps[(long)blockIdx.x * 16 + (IDX)] = __builtin_readcyclecounter(); \
+    } while (0)
+// every wave's own stamp K (0 = end of its reduce, 1 = end of its Kalman pass): the (nblocks, 8) table after the stamps
+// rows, [K * 4 + wave] -- the workgroup stamps above are wave 0's, which includes its wait for slower waves at a barrier
+#define PGPS_RSTAMP_WAVE(K)                                                                           \
+    do {                                                                                              \
+        if (ra.stamps && lane == 0)                                                                   \
+            ra.stamps[(long)gridDim.x * 16 + (long)blockIdx.x * 8 + (K) * kWaves + wave] = __builtin_readcyclecounter(); \
     } while (0)
 
 // Diagnostics (pgps_debug_resident_delay): a deterministic start skew.  The armed workgroup's publishing lane waits
@@ -309,10 +317,57 @@ __device__ __forceinline__ E res_readlane_elem(const E& e, int l) {
     unpack(v, r);
     return r;
 }
-// inclusive scan of the values lanes 0..3 hold (identity elsewhere), in place: lanes 0..3 end with the prefixes (FORWARD)
-// or the suffixes of the four
-// wave_scan_inclusive of pgps_kernels.hip.h with the per-level `if (lane takes part)` turned into a select: six levels in one
-// basic block instead of six divergent regions (PGPS_RES_SCAN_SELECT=0: the shared branching version)
+// DPP moves with bound_ctrl set and every row and bank enabled: a lane whose source lies outside its row (row_shr /
+// row_shl) or outside the wave (wave_shr / wave_shl) reads ZERO.  No `old` operand is kept, so nothing is copied ahead of
+// the move: one v_mov_b32_dpp per dword and level.
+template <int CTRL>
+__device__ __forceinline__ float res_dpp0(float x) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
+}
+template <int CTRL>
+__device__ __forceinline__ double res_dpp0(double x) {
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), CTRL, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), CTRL, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
+}
+// x where `keep`, else 1, for an x that is +0 wherever !keep: one select, on the word that holds the exponent
+__device__ __forceinline__ float res_one_unless(float x, bool keep) {
+    return __builtin_bit_cast(float, keep ? __builtin_bit_cast(int, x) : 0x3f800000);
+}
+__device__ __forceinline__ double res_one_unless(double x, bool keep) {
+    return __hiloint2double(keep ? __double2hiint(x) : 0x3ff00000, __double2loint(x));
+}
+// the all-zero element is the identity but for the unit diagonal of A (filter) / E (smoother)
+template <typename T, int D>
+__device__ __forceinline__ void res_unit_diag(FiltElem<T, D>& e, bool keep) {
+#pragma unroll
+    for (int i = 0; i < D; ++i) e.A[i * D + i] = res_one_unless(e.A[i * D + i], keep);
+}
+template <typename T, int D>
+__device__ __forceinline__ void res_unit_diag(SmthElem<T, D>& e, bool keep) {
+#pragma unroll
+    for (int i = 0; i < D; ++i) e.E[i * D + i] = res_one_unless(e.E[i * D + i], keep);
+}
+// the element the DPP pattern CTRL moves into this lane, or the identity where it has no source (`has` false): D selects
+// in place of one per dword.  Combining with the identity returns the other operand bit for bit for finite operands
+// (every product is x * 1 or y * 0 and every sum adds a zero: tests/test_res_identity.py), so every lane combines at the
+// row levels and no lane keeps its old value by a select.
+template <int CTRL, typename E>
+__device__ __forceinline__ E res_dpp_elem(const E& e, bool has) {
+    using TR = ElemTraits<E>;
+    typename TR::Scalar v[TR::N];
+    pack(e, v);
+#pragma unroll
+    for (int i = 0; i < TR::N; ++i) v[i] = res_dpp0<CTRL>(v[i]);
+    E r;
+    unpack(v, r);
+    res_unit_diag(r, has);
+    return r;
+}
+// inclusive scan over the 64 lanes of a wave, in place.  wave_scan_inclusive of pgps_kernels.hip.h without its per-level
+// `if (lane takes part)`: the four row levels combine in every lane (with the identity where the shift has no source), the
+// two cross-row levels keep the rows they do not reach by a select -- six levels in one basic block instead of six
+// divergent regions (PGPS_RES_SCAN_SELECT=0: the shared branching version)
 #ifndef PGPS_RES_SCAN_SELECT
 #define PGPS_RES_SCAN_SELECT 1
 #endif
@@ -321,6 +376,11 @@ __device__ __forceinline__ void res_wave_scan_inclusive(E& incl, int lane) {
 #if PGPS_RES_SCAN_SELECT
     using TR = ElemTraits<E>;
     const int r = lane & 15;
+    auto all = [&](const E& other) {
+        E t;
+        if (FORWARD) TR::combine(other, incl, t); else TR::combine(incl, other, t);
+        incl = t;
+    };
     auto step = [&](const E& other, bool act) {
         E t;
         if (FORWARD) TR::combine(other, incl, t); else TR::combine(incl, other, t);
@@ -332,17 +392,17 @@ __device__ __forceinline__ void res_wave_scan_inclusive(E& incl, int lane) {
         unpack(b, incl);
     };
     if constexpr (FORWARD) {
-        step(dpp_elem<kDppRowShr + 1, 0xf>(incl), r >= 1);
-        step(dpp_elem<kDppRowShr + 2, 0xf>(incl), r >= 2);
-        step(dpp_elem<kDppRowShr + 4, 0xf>(incl), r >= 4);
-        step(dpp_elem<kDppRowShr + 8, 0xf>(incl), r >= 8);
+        all(res_dpp_elem<kDppRowShr + 1>(incl, r >= 1));
+        all(res_dpp_elem<kDppRowShr + 2>(incl, r >= 2));
+        all(res_dpp_elem<kDppRowShr + 4>(incl, r >= 4));
+        all(res_dpp_elem<kDppRowShr + 8>(incl, r >= 8));
         step(dpp_elem<kDppBcast15, 0xa>(incl), (lane & 16) != 0);
         step(dpp_elem<kDppBcast31, 0xc>(incl), lane >= 32);
     } else {
-        step(dpp_elem<kDppRowShl + 1, 0xf>(incl), r + 1 < 16);
-        step(dpp_elem<kDppRowShl + 2, 0xf>(incl), r + 2 < 16);
-        step(dpp_elem<kDppRowShl + 4, 0xf>(incl), r + 4 < 16);
-        step(dpp_elem<kDppRowShl + 8, 0xf>(incl), r + 8 < 16);
+        all(res_dpp_elem<kDppRowShl + 1>(incl, r + 1 < 16));
+        all(res_dpp_elem<kDppRowShl + 2>(incl, r + 2 < 16));
+        all(res_dpp_elem<kDppRowShl + 4>(incl, r + 4 < 16));
+        all(res_dpp_elem<kDppRowShl + 8>(incl, r + 8 < 16));
         const int row = lane >> 4;
         step(shfl_idx_elem(incl, ((row + 1) & 3) * 16), row < 3);
         step(shfl_idx_elem(incl, ((row + 2) & 3) * 16), row < 2);
@@ -352,43 +412,45 @@ __device__ __forceinline__ void res_wave_scan_inclusive(E& incl, int lane) {
 #endif
 }
 
+// inclusive scan of the values lanes 0..3 hold (identity elsewhere), in place: lanes 0..3 end with the prefixes (FORWARD)
+// or the suffixes of the four
 template <typename E, bool FORWARD>
 __device__ __forceinline__ void res_scan4(E& x, int lane) {
     using TR = ElemTraits<E>;
     const int r = lane & 15;
-    auto step = [&](const E& other, bool act) {
+    auto all = [&](const E& other) {
         E t;
         if (FORWARD) TR::combine(other, x, t); else TR::combine(x, other, t);
-        if (act) x = t;
+        x = t;
     };
     if constexpr (FORWARD) {
-        step(dpp_elem<kDppRowShr + 1, 0xf>(x), r >= 1);
-        step(dpp_elem<kDppRowShr + 2, 0xf>(x), r >= 2);
+        all(res_dpp_elem<kDppRowShr + 1>(x, r >= 1));
+        all(res_dpp_elem<kDppRowShr + 2>(x, r >= 2));
     } else {
-        step(dpp_elem<kDppRowShl + 1, 0xf>(x), r + 1 < 16);
-        step(dpp_elem<kDppRowShl + 2, 0xf>(x), r + 2 < 16);
+        all(res_dpp_elem<kDppRowShl + 1>(x, r + 1 < 16));
+        all(res_dpp_elem<kDppRowShl + 2>(x, r + 2 < 16));
     }
 }
-// `total` is valid in lane kWaves - 1 (FORWARD) / lane 0 (backward) of every wave only
-template <typename E, bool FORWARD>
-__device__ __forceinline__ void res_block_scan_exclusive(const E& mine, E& excl, E& total, typename ElemTraits<E>::Scalar* lds) {
+// Exclusive workgroup scan.  The workgroup's total exists in ONE lane as soon as the cross-wave level is done -- lane 3
+// (FORWARD) / lane 0 of every wave -- and `publish(total)` runs there at once, in wave 0 (threadIdx.x 3 / 0): the
+// neighbour that waits for it no longer waits for the v_readlane broadcast, the final combine and the barrier below.
+template <typename E, bool FORWARD, typename PUB>
+__device__ __forceinline__ void res_block_scan_exclusive(const E& mine, E& excl, typename ElemTraits<E>::Scalar* lds, PUB&& publish) {
     using TR = ElemTraits<E>;
     static_assert(kWaves == 4, "four wave totals in lanes 0..3");
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
     E incl = mine;
     res_wave_scan_inclusive<E, FORWARD>(incl, lane);
-    E wex = wave_shift1<E, FORWARD>(incl);
-    if (FORWARD ? (lane == 0) : (lane == kWave - 1)) TR::identity(wex);
+    // the neighbour lane's inclusive value; the identity in the first (FORWARD) / last lane, which has none
+    E wex = FORWARD ? res_dpp_elem<kDppWaveShr1>(incl, lane != 0) : res_dpp_elem<kDppWaveShl1>(incl, lane != kWave - 1);
     if (FORWARD ? (lane == kWave - 1) : (lane == 0)) rec_store(lds + wave * TR::N, incl);
     __syncthreads();
     E t;
     TR::identity(t);
     if (lane < kWaves) rec_load(lds + lane * TR::N, t);
     res_scan4<E, FORWARD>(t, lane);
-    // the workgroup's total stays where the scan left it: lane 3 (FORWARD) / lane 0 of every wave -- the one lane that
-    // publishes it reads it there (kResTotalLane); broadcasting it costs 28 v_readlane and as many registers for nothing
-    total = t;
+    if (threadIdx.x == (FORWARD ? kWaves - 1 : 0)) publish(t);
     // (no branch on the wave's position: the first / last wave combines with the identity, which is exact)
     typename TR::Scalar pv[TR::N], iv[TR::N];
     {
@@ -612,24 +674,22 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
             if (full) stream(std::true_type{}); else stream(std::false_type{});
         }
     }
+    PGPS_RSTAMP_WAVE(0);
     PGPS_RSTAMP(1);
     FE excl;
-    {
-        FE total;
-        res_block_scan_exclusive<FE, true>(agg, excl, total, lds);
-        PGPS_RSTAMP(2);
-        if (threadIdx.x == kWaves - 1) {            // the lane the forward scan leaves the workgroup's total in
-            T v[NF];
-            pack(total, v);
-            if constexpr (SKEW) res_skew(ra, tile, 1);
+    // the workgroup's total is published from inside the scan, by the lane that holds it first (threadIdx.x 3)
+    res_block_scan_exclusive<FE, true>(agg, excl, lds, [&](const FE& total) {
+        T v[NF];
+        pack(total, v);
+        if constexpr (SKEW) res_skew(ra, tile, 1);
 #pragma unroll
-            for (int i = 0; i < NF; ++i) pub_store(a.spine + (long)tile * NF + i, v[i]);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            pub_store(ra.flags1 + tile, ra.epoch);
-            if constexpr (SKEW) res_wstamp(ra, tile, 10);
-            res_arrive(ra.bar, tile);
-        }
-    }
+        for (int i = 0; i < NF; ++i) pub_store(a.spine + (long)tile * NF + i, v[i]);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        pub_store(ra.flags1 + tile, ra.epoch);
+        if constexpr (SKEW) res_wstamp(ra, tile, 10);
+        res_arrive(ra.bar, tile);
+    });
+    PGPS_RSTAMP(2);
     // (the wait: below, where the carry is taken -- for the left neighbour alone when its total has forgotten its past)
 
     // ---------------------------------------------------------------------------------------------
@@ -800,6 +860,7 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
     }
     if constexpr (!SMOOTH) {
         // the filter alone: the workgroup's log-likelihood partial out, one arrival; workgroup 0 sums when everyone has arrived
+        PGPS_RSTAMP_WAVE(1);
         PGPS_RSTAMP(5);
         const double v = ll.value();
         const double t = block_sum_double(v, lds_ll);
@@ -839,23 +900,31 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
         for (int q = 0; q < MAT; ++q) Lg[q] = q < SYM ? e.L[q < SYM ? q : 0] : e.g[q < SYM ? 0 : q - SYM];
         store_rec<T, MAT>(myrec + j * MAT, Lg);
     }
+    PGPS_RSTAMP_WAVE(1);
     PGPS_RSTAMP(5);
     SE sexcl;
+    // the smoothing total first, from inside the scan (threadIdx.x 0): the left neighbour waits for it alone
+    res_block_scan_exclusive<SE, false>(sagg, sexcl, lds, [&](const SE& stotal) {
+        T vv[NS];
+        pack(stotal, vv);
+        if constexpr (SKEW) res_skew(ra, tile, 2);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) pub_store(a.sspine + (long)tile * NS + i, vv[i]);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        pub_store(ra.flags2 + tile, ra.epoch);
+    });
+    PGPS_RSTAMP(6);
     {
+        // then the log-likelihood partial, which only workgroup 0 reads, at the very end: its fp64 log and workgroup sum
+        // run while this workgroup would wait for its right neighbour anyway (same values, same order of summation).
+        // The arrival at barrier 2 comes after BOTH records -- the smoothing total above and the partial here -- are
+        // drained, by the lane that stored them: the general fold below and workgroup 0's final sum wait for every
+        // arrival and then read both kinds.
         const double v = ll.value();
         const double t = block_sum_double(v, lds_ll);
-        SE stotal;
-        res_block_scan_exclusive<SE, false>(sagg, sexcl, stotal, lds);
-        PGPS_RSTAMP(6);
-        if (threadIdx.x == 0) {                     // (the backward scan leaves its total in lane 0)
-            T vv[NS];
-            pack(stotal, vv);
-            if constexpr (SKEW) res_skew(ra, tile, 2);
-#pragma unroll
-            for (int i = 0; i < NS; ++i) pub_store(a.sspine + (long)tile * NS + i, vv[i]);
+        if (threadIdx.x == 0) {
             pub_store(a.llpart + tile, t);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            pub_store(ra.flags2 + tile, ra.epoch);
             if constexpr (SKEW) res_wstamp(ra, tile, 11);
             res_arrive(ra.bar2, tile);
         }

@@ -55,6 +55,8 @@ def _declare(lib):
     if hasattr(lib, "pgps_set_resident"):       # (absent from libraries built before round 5: A/B runs load those)
         lib.pgps_set_resident.argtypes = [P, c_int]
         lib.pgps_resident_stamps.argtypes = [P, P, c_int, ctypes.POINTER(c_int)]
+    if hasattr(lib, "pgps_resident_wave_stamps"):
+        lib.pgps_resident_wave_stamps.argtypes = [P, P, c_int, ctypes.POINTER(c_int)]
     if hasattr(lib, "pgps_debug_resident_delay"):
         lib.pgps_debug_resident_delay.argtypes = [P, c_int, c_int, c_int]
     if hasattr(lib, "pgps_set_shortcut"):
@@ -223,6 +225,16 @@ class Context:
         check(self, self.lib.pgps_resident_stamps(self.handle, None, 0, ctypes.byref(n)), "pgps_resident_stamps")
         out = np.zeros((max(n.value, 1), 16), np.int64)
         check(self, self.lib.pgps_resident_stamps(self.handle, _ptr(out), n.value, ctypes.byref(n)), "pgps_resident_stamps")
+        return out[:n.value]
+
+    def resident_wave_stamps(self):
+        """(workgroups, 8) cycle stamps of the same launch as resident_stamps(): [k * 4 + wave] = the end of that wave's reduce
+        (k = 0) / Kalman pass (k = 1)."""
+        n = c_int(0)
+        check(self, self.lib.pgps_resident_wave_stamps(self.handle, None, 0, ctypes.byref(n)), "pgps_resident_wave_stamps")
+        out = np.zeros((max(n.value, 1), 8), np.int64)
+        check(self, self.lib.pgps_resident_wave_stamps(self.handle, _ptr(out), n.value, ctypes.byref(n)),
+              "pgps_resident_wave_stamps")
         return out[:n.value]
 
     def debug_resident_delay(self, tile, phase=1, microseconds=200):
