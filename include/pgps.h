@@ -244,6 +244,29 @@ int pgps_pks_dev_f64(pgps_ctx*, long N, int d, const double* Fs, const double* Q
 int pgps_pks_dev_f32(pgps_ctx*, long N, int d, const float* Fs, const float* Qs, const float* fms,
                      const float* fPs, float* sms, float* sPs);
 
+/* ---- joint posterior draws: parallel backward sampling ---------------
+ * S joint draws of x_0..x_{N-1} | ys from Fs, Qs and pgps_pkf_* output; d <= PGPS_MAX_DIM_LANE (else
+ * PGPS_E_UNSUPPORTED_DIM).  x_{N-1} = fm_{N-1} + C(fP_{N-1}) z_{N-1}, x_k = E_k x_{k+1} + g_k + C(L_k) z_k with
+ * (E_k, g_k, L_k) the smoothing element of step k and C the lower semidefinite Cholesky factor.
+ * z (S,N,d) caller's standard normals, or NULL = the library's draws for samples s0..s0+S-1 under seed (Philox4x32-10 +
+ * Box-Muller: a fixed function of (seed, s0 + s, k, i), whatever the launch geometry; s0 + S <= 2^32).
+ * out: (S,N,d) states if H == NULL, else (S,N) of H x_k  (H: d values, host memory).
+ * float32 obeys pgps_set_f32_policy as pgps_pks_f32 does: a promoted call runs in fp64 on the fp64 draws, rounds its
+ * results and raises PGPS_STATUS_F32_PROMOTED. */
+int pgps_pks_sample_f64(pgps_ctx*, long N, int d, const double* Fs, const double* Qs, const double* fms, const double* fPs,
+                        int S, long s0, unsigned long long seed, const double* z, const double* H, double* out);
+int pgps_pks_sample_f32(pgps_ctx*, long N, int d, const float* Fs, const float* Qs, const float* fms, const float* fPs,
+                        int S, long s0, unsigned long long seed, const float* z, const float* H, float* out);
+int pgps_pks_sample_dev_f64(pgps_ctx*, long N, int d, const double* Fs, const double* Qs, const double* fms,
+                            const double* fPs, int S, long s0, unsigned long long seed, const double* z, const double* H,
+                            double* out);
+int pgps_pks_sample_dev_f32(pgps_ctx*, long N, int d, const float* Fs, const float* Qs, const float* fms,
+                            const float* fPs, int S, long s0, unsigned long long seed, const float* z, const float* H,
+                            float* out);
+/* the library's draws themselves, (S,N,d), device pointer */
+int pgps_sample_normals_dev_f64(pgps_ctx*, long N, int d, int S, long s0, unsigned long long seed, double* z);
+int pgps_sample_normals_dev_f32(pgps_ctx*, long N, int d, int S, long s0, unsigned long long seed, float* z);
+
 /* ---- filter + smoother: pssgp/kalman/parallel.py:199-201 (pkfs) ------------------------
  * One fused three-launch pass.  Also returns the filtered moments and the log-likelihood
  * (the reference's pkfs drops them; StateSpaceGP runs the filter a second time for ll,
@@ -309,6 +332,15 @@ int pgps_lti_predict_f64(pgps_ctx*, long N, long K, int d, const double* F, cons
 int pgps_lti_predict_dev_f64(pgps_ctx*, long N, long K, int d, const double* F, const double* Pinf, const double* H,
                              double R, const double* ts, const double* ys, double t0, const double* tq, double* mean,
                              double* var, double* ll);
+/* model-level sampler, as pgps_lti_predict_*: merge sorted ts / tq (its query slots give the output column), missing
+ * observations at the query rows, discretise, filter, sample; out (S,K) = H x at the K queries of samples s0..s0+S-1
+ * (the library's draws under seed); ll (nullable) = training log-likelihood.  1 <= d <= PGPS_MAX_DIM_LANE, fp64. */
+int pgps_lti_sample_f64(pgps_ctx*, long N, long K, int d, const double* F, const double* Pinf, const double* H, double R,
+                        const double* ts, const double* ys, double t0, const double* tq, int S, long s0,
+                        unsigned long long seed, double* out, double* ll);
+int pgps_lti_sample_dev_f64(pgps_ctx*, long N, long K, int d, const double* F, const double* Pinf, const double* H,
+                            double R, const double* ts, const double* ys, double t0, const double* tq, int S, long s0,
+                            unsigned long long seed, double* out, double* ll);
 
 /* B models over the same series in one set of launches (hyper-parameter grids, HMC chains, multi-start optimisation
  * -- the realistic series, N = 1e3..1e5, are launch-latency bound one model at a time).  `models` is HOST memory,
@@ -459,6 +491,14 @@ int pgps_seq_ks_f64(long N, int d, const double* Fs, const double* ms, const dou
                     const double* Pps, double* sms, double* sPs);
 int pgps_seq_ks_f32(long N, int d, const float* Fs, const float* ms, const float* Ps, const float* mps,
                     const float* Pps, float* sms, float* sPs);
+/* host twins of the sampler (any d <= PGPS_MAX_DIM): the same definition and the same draws as pgps_pks_sample_* /
+ * pgps_sample_normals_dev_*, host pointers, no context */
+int pgps_seq_ks_sample_f64(long N, int d, const double* Fs, const double* Qs, const double* fms, const double* fPs, int S,
+                           long s0, unsigned long long seed, const double* z, const double* H, double* out);
+int pgps_seq_ks_sample_f32(long N, int d, const float* Fs, const float* Qs, const float* fms, const float* fPs, int S,
+                           long s0, unsigned long long seed, const float* z, const float* H, float* out);
+int pgps_seq_sample_normals_f64(long N, int d, int S, long s0, unsigned long long seed, double* z);
+int pgps_seq_sample_normals_f32(long N, int d, int S, long s0, unsigned long long seed, float* z);
 
 /* ---- host helper: the balancing sweep of balance_ss (pssgp/kernels/math_utils.py:10-29, numba in the reference) ----
  * scale[d] = accumulated diagonal scaling after n_iter sweeps over F (d,d).  Host pointers, no context. */

@@ -106,6 +106,8 @@ extern "C" int pgps_destroy(pgps_ctx* ctx) {
         if (b.p) (void)hipFree(b.p);
     for (auto& b : ctx->wide)
         if (b.p) (void)hipFree(b.p);
+    if (ctx->smp.p) (void)hipFree(ctx->smp.p);
+    if (ctx->smp_wide.p) (void)hipFree(ctx->smp_wide.p);
     if (ctx->probe_host) (void)hipHostFree(ctx->probe_host);
     for (auto& e : ctx->ev_pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -2287,6 +2289,219 @@ extern "C" int pgps_lti_predict_dev_f64(pgps_ctx* c, long N, long K, int d, cons
                                         const double* tq, double* mean, double* var, double* ll) {
     if (K < 1) return PGPS_E_INVALID;
     return lti_dev(c, N, K, d, F, Pinf, H, R, ts, ys, t0, tq, mean, var, ll);
+}
+
+// ---------------------------------------------------------------------------------------------
+// joint posterior draws: backward sampling (pgps_sample.hip.h)
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+static int sample_dispatch(pgps_ctx* ctx, int d, const SampleArgs<T>& a) {
+    switch (d) {
+        case 1: return launch_sample<T, 1>(ctx, a);
+        case 2: return launch_sample<T, 2>(ctx, a);
+        case 3: return launch_sample<T, 3>(ctx, a);
+        case 4: return launch_sample<T, 4>(ctx, a);
+        case 5: return launch_sample<T, 5>(ctx, a);
+        case 6: return launch_sample<T, 6>(ctx, a);
+        default: return PGPS_E_UNSUPPORTED_DIM;
+    }
+}
+
+// the float32 call `a` in fp64 arithmetic: widened inputs (and z), the fp64 draws where the library draws, rounded output
+static int sample_run_wide(pgps_ctx* ctx, int d, const SampleArgs<float>& a) {
+    const size_t n = (size_t)a.N, dd = (size_t)d * d, S = (size_t)a.S;
+    const size_t nz = a.z ? S * n * d : 0, nout = S * (size_t)a.out_rows * (a.proj ? 1 : d);
+    TRY(ensure(ctx, ctx->wide[2], n * dd * sizeof(double)));
+    TRY(ensure(ctx, ctx->wide[3], n * dd * sizeof(double)));
+    TRY(ensure(ctx, ctx->wide[5], n * d * sizeof(double)));
+    TRY(ensure(ctx, ctx->wide[6], n * dd * sizeof(double)));
+    TRY(ensure(ctx, ctx->smp_wide, (nz + nout + 32) * sizeof(double)));
+    double* zw = (double*)ctx->smp_wide.p;
+    double* ow = zw + (nz + 31) / 32 * 32;
+    pgps::ConvJobs cj{};
+    const void* src[5] = {a.Fs, a.Qs, a.fms, a.fPs, a.z};
+    void* dst[5] = {ctx->wide[2].p, ctx->wide[3].p, ctx->wide[5].p, ctx->wide[6].p, zw};
+    const size_t cnt[5] = {n * dd, n * dd, n * d, n * dd, nz};
+    int nj = 0;
+    size_t most = 0;
+    for (int i = 0; i < 5; ++i) {
+        if (!cnt[i]) continue;
+        cj.src[nj] = src[i]; cj.dst[nj] = dst[i]; cj.n[nj] = (long)cnt[i];
+        most = std::max(most, cnt[i]);
+        ++nj;
+    }
+    hipLaunchKernelGGL(pgps::k_widen_many, dim3((unsigned)std::min<size_t>(4096, (most + 255) / 256), (unsigned)nj), dim3(256), 0,
+                       ctx->stream, cj);
+    SampleArgs<double> b{};
+    b.N = a.N; b.S = a.S; b.s0 = a.s0; b.seed = a.seed;
+    b.Fs = (const double*)ctx->wide[2].p; b.Qs = (const double*)ctx->wide[3].p;
+    b.fms = (const double*)ctx->wide[5].p; b.fPs = (const double*)ctx->wide[6].p;
+    b.z = a.z ? zw : nullptr;
+    b.proj = a.proj;
+    for (int i = 0; i < PGPS_MAX_DIM_LANE; ++i) b.h[i] = (double)a.h[i];
+    b.out = ow; b.out_rows = a.out_rows; b.qslot = a.qslot;
+    TRY(sample_dispatch<double>(ctx, d, b));
+    hipLaunchKernelGGL(pgps::k_narrow, dim3((unsigned)std::min<size_t>(4096, (nout + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (long)nout, (const double*)ow, a.out);
+    HIPCHK(ctx, hipGetLastError());
+    ctx->host_flags |= PGPS_STATUS_F32_PROMOTED;
+    return PGPS_OK;
+}
+
+// float32: the policy of pgps_pks_f32 -- the dense-grid probe decides between the float32 kernels and the fp64 ones
+static int sample_f32_call(pgps_ctx* ctx, int d, const SampleArgs<float>& a) {
+    int fixed = -1, nsamp = 0, dense = 0;
+    TRY(f32_probe_launch(ctx, a.N, d, a.Fs, &fixed, &nsamp));
+    if (fixed == 0) return sample_dispatch<float>(ctx, d, a);
+    if (fixed == 1) return sample_run_wide(ctx, d, a);
+    TRY(f32_probe_result(ctx, nsamp, &dense));
+    ctx->f32_last_promoted = dense;
+    return dense ? sample_run_wide(ctx, d, a) : sample_dispatch<float>(ctx, d, a);
+}
+
+template <typename T>
+static int pks_sample_dev(pgps_ctx* ctx, long N, int d, const T* Fs, const T* Qs, const T* fms, const T* fPs, int S, long s0,
+                          unsigned long long seed, const T* z, const T* H, T* out) {
+    RoctxRange range_("parallel_sampler");
+    if (!ctx || N < 1 || S < 1 || s0 < 0 || s0 + S > 0xffffffffL || !Fs || !Qs || !fms || !fPs || !out) return PGPS_E_INVALID;
+    if (d < 1 || d > PGPS_MAX_DIM_LANE) return PGPS_E_UNSUPPORTED_DIM;
+    if (!aligned16(Fs) || !aligned16(Qs) || !aligned16(fms) || !aligned16(fPs)) return PGPS_E_INVALID;
+    SampleArgs<T> a{};
+    a.N = N; a.Fs = Fs; a.Qs = Qs; a.fms = fms; a.fPs = fPs;
+    a.S = S; a.s0 = s0; a.seed = seed; a.z = z;
+    a.proj = H ? 1 : 0;
+    for (int i = 0; i < d && H; ++i) a.h[i] = H[i];
+    a.out = out; a.out_rows = N; a.qslot = nullptr;
+    if constexpr (sizeof(T) == 4) return sample_f32_call(ctx, d, a);
+    else return sample_dispatch<T>(ctx, d, a);
+}
+
+template <typename T>
+static int pks_sample_host(pgps_ctx* ctx, long N, int d, const T* Fs, const T* Qs, const T* fms, const T* fPs, int S, long s0,
+                           unsigned long long seed, const T* z, const T* H, T* out) {
+    if (!ctx || N < 1 || S < 1 || !Fs || !Qs || !fms || !fPs || !out) return PGPS_E_INVALID;
+    if (d < 1 || d > PGPS_MAX_DIM_LANE) return PGPS_E_UNSUPPORTED_DIM;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)N, dd = (size_t)d * d, nout = (size_t)S * n * (H ? 1 : d);
+    T *dFs, *dQs, *dfms, *dfPs, *dz = nullptr, *dout;
+    TRY(stage_in(ctx, ctx->st[1], Fs, n * dd, &dFs));
+    TRY(stage_in(ctx, ctx->st[2], Qs, n * dd, &dQs));
+    TRY(stage_in(ctx, ctx->st[5], fms, n * d, &dfms));
+    TRY(stage_in(ctx, ctx->st[6], fPs, n * dd, &dfPs));
+    if (z) TRY(stage_in(ctx, ctx->st[7], z, (size_t)S * n * d, &dz));
+    TRY(stage_in<T>(ctx, ctx->st[8], nullptr, nout, &dout));
+    TRY(pks_sample_dev<T>(ctx, N, d, dFs, dQs, dfms, dfPs, S, s0, seed, dz, H, dout));
+    TRY(stage_out(ctx, out, dout, nout));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PGPS_OK;
+}
+
+template <typename T>
+static int sample_normals_dev(pgps_ctx* ctx, long N, int d, int S, long s0, unsigned long long seed, T* z) {
+    if (!ctx || N < 1 || d < 1 || S < 1 || s0 < 0 || s0 + S > 0xffffffffL || !z) return PGPS_E_INVALID;
+    return launch_sample_normals<T>(ctx, N, d, S, s0, seed, z);
+}
+
+#define PGPS_DEFINE_SAMPLE(SUF, T)                                                                                         \
+    extern "C" int pgps_pks_sample_##SUF(pgps_ctx* c, long N, int d, const T* Fs, const T* Qs, const T* fms, const T* fPs, \
+                                         int S, long s0, unsigned long long seed, const T* z, const T* H, T* out) {        \
+        return pks_sample_host<T>(c, N, d, Fs, Qs, fms, fPs, S, s0, seed, z, H, out);                                     \
+    }                                                                                                                      \
+    extern "C" int pgps_pks_sample_dev_##SUF(pgps_ctx* c, long N, int d, const T* Fs, const T* Qs, const T* fms,          \
+                                             const T* fPs, int S, long s0, unsigned long long seed, const T* z,            \
+                                             const T* H, T* out) {                                                         \
+        return pks_sample_dev<T>(c, N, d, Fs, Qs, fms, fPs, S, s0, seed, z, H, out);                                      \
+    }                                                                                                                      \
+    extern "C" int pgps_sample_normals_dev_##SUF(pgps_ctx* c, long N, int d, int S, long s0, unsigned long long seed,     \
+                                                 T* z) {                                                                   \
+        return sample_normals_dev<T>(c, N, d, S, s0, seed, z);                                                            \
+    }
+
+PGPS_DEFINE_SAMPLE(f64, double)
+PGPS_DEFINE_SAMPLE(f32, float)
+
+// the model-level sampler: merge (k_merge_sorted: its qslot is the output column), discretisation, filter over the N + K
+// steps with the query rows missing, backward sampling projected through H at the query rows only
+static int lti_sample_dev(pgps_ctx* ctx, long N, long K, int d, const double* F, const double* Pinf, const double* H, double R,
+                          const double* ts, const double* ys, double t0, const double* tq, int S, long s0,
+                          unsigned long long seed, double* out, double* ll) {
+    if (!ctx || N < 1 || K < 1 || S < 1 || s0 < 0 || s0 + S > 0xffffffffL || !F || !Pinf || !H || !ts || !ys || !tq || !out)
+        return PGPS_E_INVALID;
+    if (d < 1 || d > PGPS_MAX_DIM_LANE) return PGPS_E_UNSUPPORTED_DIM;
+    if (N + K > 0x7fffffffL) return PGPS_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t m = (size_t)(N + K), dd = (size_t)d * d;
+    double *tsm, *ysm, *model, *Fs, *Qs, *fms, *fPs, *dll;
+    int* qslot;
+    TRY(stage_in<double>(ctx, ctx->lti[1], nullptr, m, &tsm));
+    TRY(stage_in<double>(ctx, ctx->lti[2], nullptr, m, &ysm));
+    TRY(stage_in<int>(ctx, ctx->lti[3], nullptr, m, &qslot));
+    TRY(launch_merge<double>(ctx, N, K, ts, ys, tq, tsm, ysm, qslot));
+    TRY(lti_model_in(ctx, d, F, Pinf, H, &model));
+    TRY(stage_in<double>(ctx, ctx->lti[4], nullptr, m * dd, &Fs));
+    TRY(stage_in<double>(ctx, ctx->lti[5], nullptr, m * dd, &Qs));
+    TRY(stage_in<double>(ctx, ctx->lti[6], nullptr, m * dd, &fPs));
+    TRY(stage_in<double>(ctx, ctx->lti[7], nullptr, m * d, &fms));
+    TRY(stage_in<double>(ctx, ctx->st[11], nullptr, 2, &dll));
+    TRY(disc_dev<double>(ctx, (long)m, d, model, model + dd, tsm, t0, Fs, Qs));
+    TRY(pkf_dev<double>(ctx, (long)m, d, model + dd, Fs, Qs, model + 2 * dd, R, ysm, fms, fPs, ll ? ll : dll));
+    SampleArgs<double> a{};
+    a.N = (long)m; a.Fs = Fs; a.Qs = Qs; a.fms = fms; a.fPs = fPs;
+    a.S = S; a.s0 = s0; a.seed = seed; a.z = nullptr;
+    a.proj = 1;
+    for (int i = 0; i < d; ++i) a.h[i] = H[i];
+    a.out = out; a.out_rows = K; a.qslot = qslot;
+    return sample_dispatch<double>(ctx, d, a);
+}
+
+static int lti_sample_host(pgps_ctx* ctx, long N, long K, int d, const double* F, const double* Pinf, const double* H, double R,
+                           const double* ts, const double* ys, double t0, const double* tq, int S, long s0,
+                           unsigned long long seed, double* out, double* ll) {
+    if (!ctx || N < 1 || K < 1 || S < 1 || !ts || !ys || !tq || !out) return PGPS_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nout = (size_t)S * (size_t)K;
+    {
+        SmallStage st(ctx, 2 * SmallStage::up((size_t)N * 8) + SmallStage::up((size_t)K * 8), SmallStage::up(nout * 8) + 16);
+        if (st.ok) {
+            double llh = 0.0;
+            double* dts_ = st.in(ts, (size_t)N);
+            double* dys_ = st.in(ys, (size_t)N);
+            double* dtq_ = st.in(tq, (size_t)K);
+            double* dll_ = st.out(&llh, 1);
+            double* dout_ = st.out(out, nout);
+            TRY(st.send());
+            TRY(lti_sample_dev(ctx, N, K, d, F, Pinf, H, R, dts_, dys_, t0, dtq_, S, s0, seed, dout_, dll_));
+            TRY(st.finish());
+            if (ll) *ll = llh;
+            return std::isfinite(llh) ? PGPS_OK : PGPS_E_NUMERIC;
+        }
+    }
+    double *dts, *dys, *dtq, *dout, *dll;
+    TRY(stage_in(ctx, ctx->st[10], ts, (size_t)N, &dts));
+    TRY(stage_in(ctx, ctx->st[4], ys, (size_t)N, &dys));
+    TRY(stage_in(ctx, ctx->st[3], tq, (size_t)K, &dtq));
+    TRY(stage_in<double>(ctx, ctx->st[8], nullptr, nout, &dout));
+    TRY(stage_in<double>(ctx, ctx->st[9], nullptr, 2, &dll));
+    TRY(lti_sample_dev(ctx, N, K, d, F, Pinf, H, R, dts, dys, t0, dtq, S, s0, seed, dout, dll));
+    TRY(stage_out(ctx, out, dout, nout));
+    double llh = 0.0;
+    TRY(stage_out(ctx, &llh, dll, 1));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (ll) *ll = llh;
+    return std::isfinite(llh) ? PGPS_OK : PGPS_E_NUMERIC;
+}
+
+extern "C" int pgps_lti_sample_f64(pgps_ctx* c, long N, long K, int d, const double* F, const double* Pinf, const double* H,
+                                   double R, const double* ts, const double* ys, double t0, const double* tq, int S, long s0,
+                                   unsigned long long seed, double* out, double* ll) {
+    if (!F || !Pinf || !H) return PGPS_E_INVALID;
+    if (d < 1 || d > PGPS_MAX_DIM_LANE) return PGPS_E_UNSUPPORTED_DIM;
+    return lti_sample_host(c, N, K, d, F, Pinf, H, R, ts, ys, t0, tq, S, s0, seed, out, ll);
+}
+extern "C" int pgps_lti_sample_dev_f64(pgps_ctx* c, long N, long K, int d, const double* F, const double* Pinf,
+                                       const double* H, double R, const double* ts, const double* ys, double t0,
+                                       const double* tq, int S, long s0, unsigned long long seed, double* out, double* ll) {
+    return lti_sample_dev(c, N, K, d, F, Pinf, H, R, ts, ys, t0, tq, S, s0, seed, out, ll);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -59,6 +59,8 @@ struct pgps_ctx {
     DevBuf pin_d;                       // its device twin
     DevBuf gadj;                        // fused-path adjoint gradient (pgps_gpadj.hip.h): kept states of the forward pass, workgroup partials
     DevBuf wide[9];                     // fp64 copies of a promoted float32 call's arrays: P0, H, Fs, Qs, ys, fms, fPs, sms, sPs
+    DevBuf smp;                         // backward sampler (pgps_sample.hip.h): lane suffixes and spine of every sample group
+    DevBuf smp_wide;                    // ... a promoted float32 call's fp64 draws and output
     void* comm = nullptr;               // ncclComm_t (RCCL) of a series sharded over GPUs: pgps_comm_init (pgps_comm.hip)
     int comm_rank = 0, comm_nranks = 0;
     DevBuf comm_buf;                    // [rec_f | rec_s | gathered_f | gathered_s] of pgps_pkfs_seg_dev_*
@@ -279,6 +281,36 @@ int launch_gradb(pgps_ctx* ctx, long N, int nblk, const int* bsize, int np, cons
                  const double* ys, double* out_dev);
 
 enum Mode { MODE_PKF, MODE_PKS, MODE_PKFS, MODE_SEG_REDUCE, MODE_SEG_FILTER, MODE_SEG_SMOOTHER };
+
+// Joint posterior draws by backward sampling (pgps_sample.hip.h): one (dtype, d) unit per
+// 1 <= d <= PGPS_MAX_DIM_LANE (pgps_sample_inst.hip).  Sample s (0 <= s < S) uses the draws of global index s0 + s.
+template <typename T>
+struct SampleArgs {
+    long N;
+    const T* Fs;
+    const T* Qs;
+    const T* fms;
+    const T* fPs;
+    int S;
+    long s0;
+    unsigned long long seed;
+    const T* z;             // (S, N, d) standard normals of the caller, or nullptr = the library's (pgps_philox.h)
+    int proj;               // 1: write H x_k (h below), 0: the states
+    T h[PGPS_MAX_DIM_LANE];
+    T* out;                 // sample s, column c: out[(s * out_rows + c) * (proj ? 1 : d)]
+    long out_rows;
+    const int* qslot;       // nullptr: column = step; else the column of step k is qslot[k], none where < 0
+    // launch geometry and workspace (filled by launch_sample)
+    int Lc, nblocks, ngroups;
+    long nlanes;
+    T* lsuf;                // (ngroups, NREC, nlanes) field-major
+    T* spine;               // (ngroups, nblocks, NREC)
+};
+template <typename T, int D>
+int launch_sample(pgps_ctx* ctx, SampleArgs<T> a);
+// z (S, N, d) = the library's draws of samples s0 .. s0 + S - 1 (any d)
+template <typename T>
+int launch_sample_normals(pgps_ctx* ctx, long N, int d, int S, long s0, unsigned long long seed, T* z);
 
 // defined in pgps_inst.hip, one explicit instantiation per compiled (T, D)
 template <typename T, int D>

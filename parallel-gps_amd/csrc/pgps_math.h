@@ -17,7 +17,8 @@
 #pragma once
 
 #if defined(__HIPCC__)
-#define PGPS_HD __host__ __device__ __forceinline__
+// (= __forceinline__, spelled out: hipcc compiles the host-only pgps_seq_host.cpp as HIP without hip_runtime.h)
+#define PGPS_HD __host__ __device__ inline __attribute__((always_inline))
 #else
 #define PGPS_HD inline
 #endif

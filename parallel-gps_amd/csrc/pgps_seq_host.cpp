@@ -3,10 +3,12 @@
 // host C++.  The reference runs this mode on the CPU too (`--device=/cpu:0`,
 // experiments/toy_models/speed_and_stability.sh:8).  It is an explicit mode of the API, not a
 // fallback: nothing on the parallel=True path ever reaches this file.
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "../../include/pgps.h"
+#include "pgps_philox.h"
 
 namespace {
 
@@ -165,6 +167,135 @@ int seq_ks(long N, int d, const T* Fs, const T* ms, const T* Ps, const T* mps, c
     return PGPS_OK;
 }
 
+// Lower semidefinite Cholesky factor of the symmetric M (d x d, full), column (Crout) order -- pgps_philox.h psd_chol at run-time
+// d: a column whose pivot is not above tau = d eps scale is zero (scale = max_i P_ii of the filtered covariance M came from).
+template <typename T>
+void psd_chol_rt(int d, const T* M, T scale, T* C) {
+    const T tau = T(d) * pgps::CholEps<T>::v * scale;
+    for (int i = 0; i < d * d; ++i) C[i] = T(0);
+    for (int j = 0; j < d; ++j) {
+        T p = M[j * d + j];
+        for (int l = 0; l < j; ++l) p -= C[j * d + l] * C[j * d + l];
+        if (!(p > tau)) continue;
+        const T c = std::sqrt(p);
+        C[j * d + j] = c;
+        for (int i = j + 1; i < d; ++i) {
+            T q = M[i * d + j];
+            for (int l = 0; l < j; ++l) q -= C[i * d + l] * C[j * d + l];
+            C[i * d + j] = q / c;
+        }
+    }
+}
+
+// X = A^-1 B (A d x d, B d x d, both overwritten; X in B): Gaussian elimination with partial pivoting.  False if singular.
+template <typename T>
+bool lu_solve(int d, T* A, T* B) {
+    for (int c = 0; c < d; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < d; ++r)
+            if (std::fabs(A[r * d + c]) > std::fabs(A[piv * d + c])) piv = r;
+        if (!(A[piv * d + c] != T(0))) return false;
+        if (piv != c)
+            for (int j = 0; j < d; ++j) { std::swap(A[c * d + j], A[piv * d + j]); std::swap(B[c * d + j], B[piv * d + j]); }
+        for (int r = 0; r < d; ++r) {
+            if (r == c) continue;
+            const T f = A[r * d + c] / A[c * d + c];
+            if (f == T(0)) continue;
+            for (int j = 0; j < d; ++j) { A[r * d + j] -= f * A[c * d + j]; B[r * d + j] -= f * B[c * d + j]; }
+        }
+    }
+    for (int r = 0; r < d; ++r) {
+        const T inv = A[r * d + r];
+        for (int j = 0; j < d; ++j) B[r * d + j] /= inv;
+    }
+    return true;
+}
+
+// Backward sampling: x_{N-1} = fm_{N-1} + C(fP_{N-1}) z_{N-1}, x_k = E_k x_{k+1} + g_k + C(L_k) z_k with
+// (E_k, g_k, L_k) the smoothing element of step k (E = P F^T Pp^-1, g = m - E F m, L = sym(P - E F P); parallel.py:159-166).
+// The element is built once per step for all S samples.  z (S, N, d) or nullptr = the library's draws (pgps_philox.h).
+template <typename T>
+int seq_sample(long N, int d, const T* Fs, const T* Qs, const T* fms, const T* fPs, int S, long s0, unsigned long long seed,
+               const T* z, const T* H, T* out) {
+    if (N < 1 || d < 1 || S < 1 || s0 < 0 || s0 + S > 0xffffffffL || !Fs || !Qs || !fms || !fPs || !out) return PGPS_E_INVALID;
+    if (d > PGPS_MAX_DIM) return PGPS_E_UNSUPPORTED_DIM;
+    const size_t dd = (size_t)d * d;
+    Seq<T> w(d);
+    std::vector<T> x((size_t)S * d), E(dd), g(d), L(dd), C(dd), Pp(dd), A(dd), X(dd), mp(d), zv(d + 1), t(d);
+    for (long k = N - 1; k >= 0; --k) {
+        const T* m = fms + k * d;
+        const T* P = fPs + k * dd;
+        if (k == N - 1) {
+            for (size_t i = 0; i < dd; ++i) { E[i] = T(0); L[i] = T(0.5) * (P[i] + P[(i % d) * d + i / d]); }
+            for (int i = 0; i < d; ++i) g[i] = m[i];
+        } else {
+            const T* F = Fs + (k + 1) * dd;
+            w.predict(F, P, Qs + (k + 1) * dd, Pp.data());           // Pp; w.FP = F P
+            for (size_t i = 0; i < dd; ++i) { A[i] = Pp[i]; X[i] = w.FP[i]; }
+            if (!lu_solve(d, A.data(), X.data())) return PGPS_E_NUMERIC;         // X = Pp^-1 F P = E^T
+            for (int i = 0; i < d; ++i)
+                for (int j = 0; j < d; ++j) E[i * d + j] = X[j * d + i];
+            for (int i = 0; i < d; ++i) {
+                T acc = 0;
+                for (int j = 0; j < d; ++j) acc += F[i * d + j] * m[j];
+                mp[i] = acc;
+            }
+            for (int i = 0; i < d; ++i) {
+                T acc = 0;
+                for (int j = 0; j < d; ++j) acc += E[i * d + j] * mp[j];
+                g[i] = m[i] - acc;
+            }
+            for (int i = 0; i < d; ++i)
+                for (int j = 0; j < d; ++j) {
+                    T a = 0, b = 0;
+                    for (int l = 0; l < d; ++l) { a += E[i * d + l] * w.FP[l * d + j]; b += E[j * d + l] * w.FP[l * d + i]; }
+                    L[i * d + j] = T(0.5) * (P[i * d + j] + P[j * d + i]) - T(0.5) * (a + b);
+                }
+        }
+        T pmax = P[0];
+        for (int i = 1; i < d; ++i) pmax = P[i * d + i] > pmax ? P[i * d + i] : pmax;
+        psd_chol_rt(d, L.data(), pmax, C.data());
+        for (int s = 0; s < S; ++s) {
+            T* xs = x.data() + (size_t)s * d;
+            if (z) {
+                for (int i = 0; i < d; ++i) zv[i] = z[((size_t)s * N + k) * d + i];
+            } else {
+                for (int j = 0; j < (d + 1) / 2; ++j) pgps::normal_pair<T>(seed, k, (uint32_t)(s0 + s), (uint32_t)j, zv[2 * j], zv[2 * j + 1]);
+            }
+            for (int i = 0; i < d; ++i) {
+                T acc = g[i];
+                for (int j = 0; j < d; ++j) acc += E[i * d + j] * xs[j];
+                for (int j = 0; j <= i; ++j) acc += C[i * d + j] * zv[j];
+                t[i] = acc;
+            }
+            for (int i = 0; i < d; ++i) xs[i] = t[i];
+            if (H) {
+                T acc = 0;
+                for (int i = 0; i < d; ++i) acc += H[i] * xs[i];
+                out[(size_t)s * N + k] = acc;
+            } else {
+                for (int i = 0; i < d; ++i) out[((size_t)s * N + k) * d + i] = xs[i];
+            }
+        }
+    }
+    return PGPS_OK;
+}
+
+template <typename T>
+int seq_normals(long N, int d, int S, long s0, unsigned long long seed, T* z) {
+    if (N < 1 || d < 1 || S < 1 || s0 < 0 || s0 + S > 0xffffffffL || !z) return PGPS_E_INVALID;
+    for (int s = 0; s < S; ++s)
+        for (long k = 0; k < N; ++k)
+            for (int j = 0; j < (d + 1) / 2; ++j) {
+                T a, b;
+                pgps::normal_pair<T>(seed, k, (uint32_t)(s0 + s), (uint32_t)j, a, b);
+                T* o = z + ((size_t)s * N + k) * d;
+                o[2 * j] = a;
+                if (2 * j + 1 < d) o[2 * j + 1] = b;
+            }
+    return PGPS_OK;
+}
+
 }  // namespace
 
 extern "C" int pgps_seq_kf_f64(long N, int d, const double* P0, const double* Fs, const double* Qs, const double* H,
@@ -210,4 +341,19 @@ extern "C" int pgps_host_balance_f64(int d, const double* F, int n_iter, double*
             }
         }
     return PGPS_OK;
+}
+
+extern "C" int pgps_seq_ks_sample_f64(long N, int d, const double* Fs, const double* Qs, const double* fms, const double* fPs,
+                                      int S, long s0, unsigned long long seed, const double* z, const double* H, double* out) {
+    return seq_sample<double>(N, d, Fs, Qs, fms, fPs, S, s0, seed, z, H, out);
+}
+extern "C" int pgps_seq_ks_sample_f32(long N, int d, const float* Fs, const float* Qs, const float* fms, const float* fPs,
+                                      int S, long s0, unsigned long long seed, const float* z, const float* H, float* out) {
+    return seq_sample<float>(N, d, Fs, Qs, fms, fPs, S, s0, seed, z, H, out);
+}
+extern "C" int pgps_seq_sample_normals_f64(long N, int d, int S, long s0, unsigned long long seed, double* z) {
+    return seq_normals<double>(N, d, S, s0, seed, z);
+}
+extern "C" int pgps_seq_sample_normals_f32(long N, int d, int S, long s0, unsigned long long seed, float* z) {
+    return seq_normals<float>(N, d, S, s0, seed, z);
 }

@@ -106,6 +106,16 @@ def _declare(lib):
         getattr(lib, f"pgps_pkfs_seg_dev_{suf}").argtypes = [P, c_long, c_int, P, P, P, P, real, P, P, P, P, P, P]
     for dev in ("", "_dev"):
         getattr(lib, f"pgps_gp_ll_grad_blocks{dev}_f64").argtypes = [P, c_long, c_int, c_int, P, c_int, P, P, c_double, P, P]
+    u64 = ctypes.c_ulonglong
+    for suf in ("f64", "f32"):
+        for dev in ("", "_dev"):
+            getattr(lib, f"pgps_pks_sample{dev}_{suf}").argtypes = [P, c_long, c_int, P, P, P, P, c_int, c_long, u64, P, P, P]
+        getattr(lib, f"pgps_sample_normals_dev_{suf}").argtypes = [P, c_long, c_int, c_int, c_long, u64, P]
+        getattr(lib, f"pgps_seq_ks_sample_{suf}").argtypes = [c_long, c_int, P, P, P, P, c_int, c_long, u64, P, P, P]
+        getattr(lib, f"pgps_seq_sample_normals_{suf}").argtypes = [c_long, c_int, c_int, c_long, u64, P]
+    for dev in ("", "_dev"):
+        getattr(lib, f"pgps_lti_sample{dev}_f64").argtypes = [P, c_long, c_long, c_int, P, P, P, c_double, P, P, c_double, P,
+                                                             c_int, c_long, u64, P, P]
     return lib
 
 
@@ -481,6 +491,54 @@ def pks(lgssm, ms, Ps, device=0):
     get_context(device).call(f"pgps_pks_{suf}", c_long(N), c_int(d), _ptr(Fs), _ptr(Qs), _ptr(ms), _ptr(Ps),
                              _ptr(sms), _ptr(sPs))
     return sms, sPs
+
+
+def _sample_inputs(lgssm, ms, Ps, num_samples, first_sample, z, H):
+    dtype = _dtype_of(lgssm)
+    _, Fs, Qs, *_ = lgssm
+    Fs = _prep(Fs, dtype)
+    N, d = Fs.shape[0], Fs.shape[1]
+    S = int(num_samples)
+    if S < 1 or int(first_sample) < 0:
+        raise ValueError(f"num_samples must be >= 1 and first_sample >= 0, got {num_samples}, {first_sample}")
+    z = None if z is None else _prep(z, dtype, (S, N, d))
+    H = None if H is None else _prep(H, dtype, (d,))
+    return (dtype, N, d, S, Fs, _prep(Qs, dtype, (N, d, d)), _prep(ms, dtype, (N, d)), _prep(Ps, dtype, (N, d, d)), z, H)
+
+
+def pks_sample(lgssm, ms, Ps, num_samples, seed, first_sample=0, z=None, H=None, device=0):
+    """Joint posterior draws of x_0 .. x_{N-1} by parallel backward sampling (pgps_pks_sample_*): Fs, Qs of `lgssm` and
+    the filtered moments ms (N, d), Ps (N, d, d) -> (S, N, d), or (S, N) of H x_k when H (d,) is given.  z (S, N, d):
+    the standard normals to use; None = the library's draws of samples first_sample .. first_sample + S - 1 under
+    `seed` (a fixed function of (seed, sample, step, component): the host twin ks_sample draws the same)."""
+    dtype, N, d, S, Fs, Qs, ms, Ps, z, H = _sample_inputs(lgssm, ms, Ps, num_samples, first_sample, z, H)
+    suf, _ = _suffix(dtype)
+    out = np.empty((S, N) if H is not None else (S, N, d), dtype)
+    get_context(device).call(f"pgps_pks_sample_{suf}", c_long(N), c_int(d), _ptr(Fs), _ptr(Qs), _ptr(ms), _ptr(Ps),
+                             c_int(S), c_long(int(first_sample)), ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)), _ptr(z),
+                             _ptr(H), _ptr(out))
+    return out
+
+
+def lti_sample(F, Pinf, H, R, ts, ys, tq, num_samples, seed, t0=0.0, first_sample=0, device=0):
+    """Joint posterior draws of f = H x at the sorted query times `tq` (K) of any LTI state-space GP with d <= 6
+    (pgps_lti_sample_f64): merge with the sorted training times `ts`, discretisation, filter with the query rows
+    missing, backward sampling -- the (S, K) projected draws come back, nothing per step.  Larger d raises
+    PgpsError (PGPS_E_UNSUPPORTED_DIM)."""
+    F = _prep(F, np.float64)
+    d = F.shape[0]
+    Pinf, H = _prep(Pinf, np.float64, (d, d)), _prep(H, np.float64, (d,))
+    ts_a = _prep(ts, np.float64, (-1,))
+    ys_a = _prep(ys, np.float64, (-1,))
+    tq_a = _prep(tq, np.float64, (-1,))
+    N, K, S = ts_a.shape[0], tq_a.shape[0], int(num_samples)
+    if ys_a.shape[0] != N:
+        raise ValueError(f"observations has {ys_a.shape[0]} rows, the series {N} steps")
+    out = np.empty((S, K), np.float64)
+    get_context(device).call("pgps_lti_sample_f64", c_long(N), c_long(K), c_int(d), _ptr(F), _ptr(Pinf), _ptr(H),
+                             c_double(float(R)), _ptr(ts_a), _ptr(ys_a), c_double(float(t0)), _ptr(tq_a), c_int(S),
+                             c_long(int(first_sample)), ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)), _ptr(out), None)
+    return out
 
 
 def pkfs(lgssm, observations, return_filtered=False, return_loglikelihood=False, device=0):

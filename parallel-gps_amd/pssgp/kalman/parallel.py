@@ -7,7 +7,7 @@ accepted and ignored: the reference needs it to bound the depth of tfp's recursi
 """
 from .. import _backend
 
-__all__ = ["pkf", "pks", "pkfs"]
+__all__ = ["pkf", "pks", "pkfs", "pks_sample"]
 
 
 def pkf(lgssm, observations, return_loglikelihood=False, max_parallel=10000):
@@ -26,3 +26,10 @@ def pkfs(model, observations, max_parallel=10000):
     """Filter then smoother, one fused three-launch pass on the GPU (parallel.py:199-201)."""
     del max_parallel
     return _backend.pkfs(model, observations)
+
+
+def pks_sample(lgssm, ms, Ps, num_samples=1, seed=0, first_sample=0, z=None):
+    """S joint posterior draws (S, N, d) of the states from the filtered moments, by a parallel backward-sampling scan
+    on the GPU.  z (S, N, d): standard normals to use; None = the library's draws of samples
+    first_sample .. first_sample + S - 1 under `seed` (sequential.ks_sample draws the same)."""
+    return _backend.pks_sample(lgssm, ms, Ps, num_samples, seed, first_sample=first_sample, z=z)

@@ -10,7 +10,7 @@ import numpy as np
 
 from .. import _backend
 
-__all__ = ["kf", "ks", "kfs"]
+__all__ = ["kf", "ks", "kfs", "ks_sample", "sample_normals"]
 
 
 def _ptr(a):
@@ -69,3 +69,27 @@ def ks(lgssm, ms, Ps, mps, Pps):
 def kfs(model, observations):
     fms, fPs, mps, Pps = kf(model, observations, return_predicted=True)
     return ks(model, fms, fPs, mps, Pps)
+
+
+def ks_sample(lgssm, ms, Ps, num_samples=1, seed=0, first_sample=0, z=None, H=None):
+    """Host twin of parallel.pks_sample (pgps_seq_ks_sample_*): the same backward-sampling recursion and the same
+    draws, any d.  (S, N, d), or (S, N) of H x_k when H is given."""
+    lib = _backend.load_library()
+    dtype, N, d, S, Fs, Qs, ms, Ps, z, H = _backend._sample_inputs(lgssm, ms, Ps, num_samples, first_sample, z, H)
+    suf, _ = _backend._suffix(dtype)
+    out = np.empty((S, N) if H is not None else (S, N, d), dtype)
+    code = getattr(lib, f"pgps_seq_ks_sample_{suf}")(N, d, _ptr(Fs), _ptr(Qs), _ptr(ms), _ptr(Ps), S, int(first_sample),
+                                                     int(seed) & (2 ** 64 - 1), _ptr(z), _ptr(H), _ptr(out))
+    _backend.check(None, code, "pgps_seq_ks_sample")
+    return out
+
+
+def sample_normals(N, d, num_samples, seed, first_sample=0, dtype=np.float64):
+    """The library's standard normal draws (S, N, d) of samples first_sample .. first_sample + S - 1 (host)."""
+    lib = _backend.load_library()
+    suf, _ = _backend._suffix(dtype)
+    z = np.empty((int(num_samples), int(N), int(d)), dtype)
+    code = getattr(lib, f"pgps_seq_sample_normals_{suf}")(int(N), int(d), int(num_samples), int(first_sample),
+                                                         int(seed) & (2 ** 64 - 1), _ptr(z))
+    _backend.check(None, code, "pgps_seq_sample_normals")
+    return z

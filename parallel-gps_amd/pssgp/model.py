@@ -13,6 +13,7 @@ from . import config
 from .kernels.base import Kernel, _tree_ids
 from .kernels.sde_grads import leaf_parameters
 from .kalman.parallel import pkf, pkfs
+from .kalman import sequential
 from .kalman.sequential import kf, kfs
 
 
@@ -415,6 +416,48 @@ class StateSpaceGP:
         mean = sm @ H.T
         var = np.einsum("ai,nij,aj->na", H, sP, H)
         return mean, var
+
+    @_public_evaluation
+    def predict_f_samples(self, Xnew, num_samples=None, full_cov=True, full_output_cov=False, seed=None):
+        """Joint posterior draws of f at `Xnew` (GPflow's predict_f_samples): (S, K, 1), or (K, 1) when num_samples is
+        None.  parallel=True: merge, discretisation, filter and a backward-sampling scan on the device for any kernel
+        with d <= 6 (pgps_lti_sample_f64; larger d raises PgpsError); parallel=False: the host filter and its
+        backward-sampling twin, any d.  Both use the library's draws under `seed` (None: a fresh 64-bit seed per call), so
+        the two modes give the same samples at the same seed.  full_cov=False: independent draws from predict_f's
+        marginals.  Any order of Xnew; equal query times get equal values."""
+        del full_output_cov                 # (single output)
+        dtype = config.default_float()
+        S = 1 if num_samples is None else int(num_samples)
+        if S < 1:
+            raise ValueError(f"num_samples must be >= 1, got {num_samples}")
+        if seed is None:
+            seed = int(np.random.default_rng().integers(0, 2 ** 64, dtype=np.uint64))
+        xq = np.asarray(Xnew, dtype=np.float64).reshape(-1)
+        if not full_cov:
+            mean, var = self.predict_f(Xnew)
+            z = sequential.sample_normals(xq.shape[0], 1, S, seed)[:, :, 0]
+            f = np.asarray(mean, np.float64)[:, 0] + np.sqrt(np.maximum(np.asarray(var, np.float64)[:, 0], 0.0)) * z
+        else:
+            tq, inverse = np.unique(xq, return_inverse=True)          # sorted, each time once
+            ts, ys = self.data
+            squeezed_ts = np.asarray(ts, np.float64).reshape(-1)
+            if self.parallel:
+                from . import _backend
+                sde = self.kernel.get_sde()
+                fq = _backend.lti_sample(sde.F, sde.P0, sde.H, self.noise_variance, squeezed_ts,
+                                         np.asarray(ys, np.float64).reshape(-1), tq, S, seed)
+            else:
+                nan_ys = np.full((tq.shape[0], ys.shape[1]), np.nan, dtype=np.float64)
+                all_ts, all_ys, all_flags = _merge_sorted(
+                    squeezed_ts, tq, (np.asarray(ys, np.float64), nan_ys),
+                    (np.zeros(squeezed_ts.shape, dtype=bool), np.ones(tq.shape, dtype=bool)))
+                ssm = self.kernel.get_ssm(all_ts[:, None], np.reshape(self.noise_variance, (1, 1)))
+                ssm = tuple(np.asarray(a, np.float64) for a in ssm)
+                fms, fPs = kf(ssm, all_ys)
+                fq = sequential.ks_sample(ssm, fms, fPs, S, seed, H=np.asarray(ssm[3]).reshape(-1))[:, all_flags]
+            f = fq[:, inverse]
+        out = f[:, :, None].astype(dtype)
+        return out[0] if num_samples is None else out
 
     @_public_evaluation
     def maximum_log_likelihood_objective(self):
