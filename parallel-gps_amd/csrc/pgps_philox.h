@@ -72,12 +72,19 @@ PGPS_HD void normal_vec(unsigned long long seed, long k, uint32_t s, T* z) {
     }
 }
 
-// Lower semidefinite Cholesky factor of M (symmetric, packed upper triangle), plain column (Crout) order: a column whose
-// pivot p = M_jj - sum_l C_jl^2 is not above tau = D eps scale is zero -- zeros for the singular factors of repeated
-// times, query times equal to training times and noise-free (Periodic) transitions, never NaN.  C full D x D, row-major.
+// Semidefinite Cholesky factor of M (symmetric, packed upper triangle) with diagonal pivoting: C C^T = M, column by
+// column.  At each of the D steps the pivot is the largest remaining diagonal entry (the lowest index on ties); the
+// factor stops when that entry is not above tau = (D + 3) eps scale, and the remaining columns are zero -- zeros for the singular
+// factors of repeated times, query times equal to training times and noise-free (Periodic) transitions, never NaN.  With
+// pivot p:  c = A[:, p] / sqrt(A[p, p]),  A -= c c^T,  A[p, p] = 0 (it is, in exact arithmetic), c the next column of C.
+// C is not triangular: only C C^T matters.  Pivoting keeps the factor accurate where M is nearly singular (RBF and
+// product models, float32 at d >= 3): the plain column order took rounding-sized pivots first there and drew samples whose
+// covariance was wrong by a third.
 // scale = max_i P_ii of the filtered covariance M was computed from: L = P - E F P carries rounding of P's size, and a
 // pivot of that size must not pass (at a repeated time L is rounding only, and a threshold relative to L's own diagonal
-// let such a pivot through and divided L's other rounding residues by its square root).  At the last step M = P.
+// let such a pivot through and divided L's other rounding residues by its square root).  D eps for the D-term sums of
+// E F P, 3 eps for the roundings of E itself and of the subtraction: at D = 1 those alone exceed D eps (a 2-ulp pivot
+// passed at a query on a training time and moved that draw by 1e-8).  At the last step M = P.
 template <typename T> struct CholEps;
 template <> struct CholEps<double> { static constexpr double v = 0x1p-52; };
 template <> struct CholEps<float> { static constexpr float v = 0x1p-23f; };
@@ -90,27 +97,40 @@ PGPS_HD T max_diag(const T* P) {
     return m;
 }
 
-template <typename T, int D>
-PGPS_HD void psd_chol(const T* M, T scale, T* C) {
-    const T tau = T(D) * CholEps<T>::v * scale;
-#pragma unroll
-    for (int i = 0; i < D * D; ++i) C[i] = T(0);
+// The columns of the factor, one after the other: emit(j, c) gets column j (all zero once the factor has stopped).  A is
+// consumed.  The pivot column is picked by unrolled compare-and-select, never by a run-time index into A: on the device A
+// lives in registers.
+template <typename T, int D, typename Emit>
+PGPS_HD void psd_chol_columns(T* A, T scale, Emit&& emit) {
+    const T tau = T(D + 3) * CholEps<T>::v * scale;
 #pragma unroll
     for (int j = 0; j < D; ++j) {
-        T p = M[symi<D>(j, j)];
+        T best = A[symi<D>(0, 0)];
+        int p = 0;
 #pragma unroll
-        for (int l = 0; l < j; ++l) p -= C[j * D + l] * C[j * D + l];
-        if (p > tau) {
-            const T c = std::sqrt(p);
-            C[j * D + j] = c;
-#pragma unroll
-            for (int i = j + 1; i < D; ++i) {
-                T q = M[symi<D>(i, j)];
-#pragma unroll
-                for (int l = 0; l < j; ++l) q -= C[i * D + l] * C[j * D + l];
-                C[i * D + j] = q / c;
-            }
+        for (int i = 1; i < D; ++i) {
+            const T a = A[symi<D>(i, i)];
+            const bool up = a > best;
+            best = up ? a : best;
+            p = up ? i : p;
         }
+        const bool go = best > tau;
+        const T r = go ? T(1) / std::sqrt(best) : T(0);
+        T c[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            T a = A[symi<D>(i, 0)];
+#pragma unroll
+            for (int q = 1; q < D; ++q) a = p == q ? A[symi<D>(i, q)] : a;
+            c[i] = a * r;
+        }
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+#pragma unroll
+            for (int k = i; k < D; ++k) A[symi<D>(i, k)] -= c[i] * c[k];
+            A[symi<D>(i, i)] = (go && p == i) ? T(0) : A[symi<D>(i, i)];
+        }
+        emit(j, c);
     }
 }
 

@@ -2,7 +2,7 @@
 //
 // Backward sampling runs the smoother's recursion with noise:  x_{N-1} = fm_{N-1} + C(fP_{N-1}) z_{N-1},
 // x_k = E_k x_{k+1} + g_k + C(L_k) z_k, with (E_k, g_k, L_k) the smoothing element of step k (pgps_math.h smth_element)
-// and C the lower semidefinite Cholesky factor (pgps_philox.h psd_chol).  Every step is the affine map a_k = (E_k, h_k),
+// and C the diagonally pivoted semidefinite Cholesky factor (pgps_philox.h psd_chol_columns).  Every step is the affine map a_k = (E_k, h_k),
 // h_k = g_k + C(L_k) z_k (the last one (0, h_{N-1})), composed by (E_a, h_a) (x) (E_b, h_b) = (E_a E_b, E_a h_b + h_a) --
 // smth_combine without its L part -- and x_k is the h of the suffix aggregate that starts at step k.
 //
@@ -76,13 +76,13 @@ struct ElemTraits<SampElem<T, D, SG>> {
     }
 };
 
-// (E_k, g_k, C(L_k)) of step k: the smoothing element (smth_element, from F_{k+1}, Q_{k+1}, fm_k, fP_k), or (0, fm, C(fP))
-// at the last step
+// (E_k, g_k, L_k) of step k: the smoothing element (smth_element, from F_{k+1}, Q_{k+1}, fm_k, fP_k), or (0, fm, fP) at the
+// last step.  L packed symmetric; the return value is the scale of its factor's threshold, max_i fP_ii.
 template <typename T, int D>
-__device__ __forceinline__ void sample_element(const SampleArgs<T>& a, long k, T* E, T* g, T* C) {
+__device__ __forceinline__ T sample_element(const SampleArgs<T>& a, long k, T* E, T* g, T* L) {
     constexpr int MAT = D * D, SYM = Dim<D>::SYM;
     MeanCov<T, D> f;
-    T Pf[MAT], L[SYM];
+    T Pf[MAT];
     load_rec<T, D>(a.fms + k * D, f.m);
     load_rec<T, MAT>(a.fPs + k * MAT, Pf);
     sym_from_full<T, D>(Pf, f.P);
@@ -109,30 +109,37 @@ __device__ __forceinline__ void sample_element(const SampleArgs<T>& a, long k, T
 #pragma unroll
         for (int i = 0; i < SYM; ++i) L[i] = f.P[i];
     }
-    psd_chol<T, D>(L, max_diag<T, D>(f.P), C);
+    return max_diag<T, D>(f.P);
 }
 
-// h = g + C z of the group's SG samples at step k (slots past S get z = 0; nothing of theirs is written)
+// h = g + C(L) z of the group's SG samples at step k (slots past S get z = 0; nothing of theirs is written).  The factor
+// is never stored: each of its columns is added to the SG offsets as it comes out (a full D x D C next to the record would
+// not fit the registers of fp64 d = 6).  L is consumed.
 template <typename T, int D, int SG>
-__device__ __forceinline__ void sample_offsets(const SampleArgs<T>& a, long k, int s_first, const T* g, const T* C, T* h) {
+__device__ __forceinline__ void sample_offsets(const SampleArgs<T>& a, long k, int s_first, const T* g, T* L, T scale, T* h) {
+    T z[SG * D];
 #pragma unroll
     for (int j = 0; j < SG; ++j) {
         const int s = s_first + j;
-        T z[D];
         if (s >= a.S) {
 #pragma unroll
-            for (int i = 0; i < D; ++i) z[i] = T(0);
+            for (int i = 0; i < D; ++i) z[j * D + i] = T(0);
         } else if (a.z) {
 #pragma unroll
-            for (int i = 0; i < D; ++i) z[i] = a.z[((long)s * a.N + k) * D + i];
+            for (int i = 0; i < D; ++i) z[j * D + i] = a.z[((long)s * a.N + k) * D + i];
         } else {
-            normal_vec<T, D>(a.seed, k, (uint32_t)(a.s0 + s), z);
+            normal_vec<T, D>(a.seed, k, (uint32_t)(a.s0 + s), z + j * D);
         }
-        T cz[D];
-        mat_vec<T, D>(C, z, cz);
 #pragma unroll
-        for (int i = 0; i < D; ++i) h[j * D + i] = g[i] + cz[i];
+        for (int i = 0; i < D; ++i) h[j * D + i] = g[i];
     }
+    psd_chol_columns<T, D>(L, scale, [&](int col, const T* c) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < SG; ++j) {
+#pragma unroll
+            for (int i = 0; i < D; ++i) h[j * D + i] += c[i] * z[j * D + col];
+        }
+    });
 }
 
 template <typename T, int D>
@@ -149,9 +156,9 @@ __global__ __launch_bounds__(kBlock) void k_sample_reduce(const SampleArgs<T> a)
     TR::identity(acc);
     for (long k = k0; k < k1; ++k) {
         SE e, r;
-        T g[D], C[MAT];
-        sample_element<T, D>(a, k, e.E, g, C);
-        sample_offsets<T, D, SG>(a, k, grp * SG, g, C, e.h);
+        T g[D], L[Dim<D>::SYM];
+        const T scale = sample_element<T, D>(a, k, e.E, g, L);
+        sample_offsets<T, D, SG>(a, k, grp * SG, g, L, scale, e.h);
         TR::combine(acc, e, r);
         acc = r;
     }
@@ -198,9 +205,9 @@ __global__ __launch_bounds__(kBlock) void k_sample_apply(const SampleArgs<T> a) 
     const int s_first = grp * SG;
     const int width = a.proj ? 1 : D;
     for (long k = k1 - 1; k >= k0; --k) {
-        T E[MAT], g[D], C[MAT], h[SG * D];
-        sample_element<T, D>(a, k, E, g, C);
-        sample_offsets<T, D, SG>(a, k, s_first, g, C, h);
+        T E[MAT], g[D], L[Dim<D>::SYM], h[SG * D];
+        const T scale = sample_element<T, D>(a, k, E, g, L);
+        sample_offsets<T, D, SG>(a, k, s_first, g, L, scale, h);
         long col = k;
         if (a.qslot) col = a.qslot[k];
 #pragma unroll

@@ -167,23 +167,24 @@ int seq_ks(long N, int d, const T* Fs, const T* ms, const T* Ps, const T* mps, c
     return PGPS_OK;
 }
 
-// Lower semidefinite Cholesky factor of the symmetric M (d x d, full), column (Crout) order -- pgps_philox.h psd_chol at run-time
-// d: a column whose pivot is not above tau = d eps scale is zero (scale = max_i P_ii of the filtered covariance M came from).
+// Semidefinite Cholesky factor of the symmetric M (d x d, full) with diagonal pivoting -- pgps_philox.h psd_chol_columns at
+// run-time d: at each step the largest remaining diagonal entry is the pivot (the lowest index on ties), and the factor
+// stops (zero columns) when it is not above tau = (d + 3) eps scale (scale = max_i P_ii of the filtered covariance M came from).
+// M is consumed; C full, not triangular.
 template <typename T>
-void psd_chol_rt(int d, const T* M, T scale, T* C) {
-    const T tau = T(d) * pgps::CholEps<T>::v * scale;
+void psd_chol_rt(int d, T* M, T scale, T* C) {
+    const T tau = T(d + 3) * pgps::CholEps<T>::v * scale;
     for (int i = 0; i < d * d; ++i) C[i] = T(0);
     for (int j = 0; j < d; ++j) {
-        T p = M[j * d + j];
-        for (int l = 0; l < j; ++l) p -= C[j * d + l] * C[j * d + l];
-        if (!(p > tau)) continue;
-        const T c = std::sqrt(p);
-        C[j * d + j] = c;
-        for (int i = j + 1; i < d; ++i) {
-            T q = M[i * d + j];
-            for (int l = 0; l < j; ++l) q -= C[i * d + l] * C[j * d + l];
-            C[i * d + j] = q / c;
-        }
+        int p = 0;
+        for (int i = 1; i < d; ++i)
+            if (M[i * d + i] > M[p * d + p]) p = i;
+        if (!(M[p * d + p] > tau)) break;
+        const T r = T(1) / std::sqrt(M[p * d + p]);
+        for (int i = 0; i < d; ++i) C[i * d + j] = M[i * d + p] * r;
+        for (int i = 0; i < d; ++i)
+            for (int k = 0; k < d; ++k) M[i * d + k] -= C[i * d + j] * C[k * d + j];
+        M[p * d + p] = T(0);
     }
 }
 
@@ -265,7 +266,7 @@ int seq_sample(long N, int d, const T* Fs, const T* Qs, const T* fms, const T* f
             for (int i = 0; i < d; ++i) {
                 T acc = g[i];
                 for (int j = 0; j < d; ++j) acc += E[i * d + j] * xs[j];
-                for (int j = 0; j <= i; ++j) acc += C[i * d + j] * zv[j];
+                for (int j = 0; j < d; ++j) acc += C[i * d + j] * zv[j];
                 t[i] = acc;
             }
             for (int i = 0; i < d; ++i) xs[i] = t[i];

@@ -4,7 +4,10 @@ pgps_pks_sample_dev with the library's draws (z = NULL) and with z supplied, the
 step, and the host twin's steps/s.  Times are the mean of `--reps` back-to-back calls on the context's stream between two
 synchronisations, after `--warmup` calls.
 
-usage: python tools/sample_bench.py [--reps 20] [--warmup 3] [--quick]"""
+usage: python tools/sample_bench.py [--reps 20] [--warmup 3] [--quick] [--cases 2:f64,6:f64] [--samples 1,16] [--label NAME]
+
+To compare two builds of the library, run the tool once per build (PGPS_LIB=<path to the other libpgps.so>) in alternation
+and tell the lines apart by --label."""
 import argparse
 import ctypes
 import json
@@ -48,12 +51,17 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--quick", action="store_true", help="N = 2^16 only")
+    ap.add_argument("--cases", default="2:f64,3:f64,6:f32", help="d:dtype pairs")
+    ap.add_argument("--samples", default="1,4,16,64", help="sample counts S")
+    ap.add_argument("--full-only", action="store_true", help="N = 2^20 only")
+    ap.add_argument("--label", default=None, help="copied into every output line")
     args = ap.parse_args()
     ctx = _backend.get_context()
-    for d, dt in ((2, np.float64), (3, np.float64), (6, np.float32)):
+    cases = [(int(c.split(":")[0]), {"f64": np.float64, "f32": np.float32}[c.split(":")[1]]) for c in args.cases.split(",")]
+    for d, dt in cases:
         suf, real = _backend._suffix(dt)
         sde = model(d).get_sde()
-        for N in ((1 << 16,) if args.quick else (1 << 16, 1 << 20)):
+        for N in ((1 << 16,) if args.quick else (1 << 20,) if args.full_only else (1 << 16, 1 << 20)):
             ts = np.cumsum(np.full(N, 0.05))
             Fs, Qs = _backend.discretise(np.asarray(sde.F, np.float64), np.asarray(sde.P0, np.float64), ts)
             host = {"Fs": Fs.astype(dt), "Qs": Qs.astype(dt), "P0": np.asarray(sde.P0, dt), "H": np.asarray(sde.H, dt).reshape(-1),
@@ -76,7 +84,7 @@ def main():
             t = time.perf_counter()
             ks_sample((None, host["Fs"][:4096], host["Qs"][:4096]), fms[:4096], fPs[:4096], 1, 1)
             host_rate = 4096 / (time.perf_counter() - t)
-            for S in (1, 4, 16, 64):
+            for S in (int(v) for v in args.samples.split(",")):
                 z = ctx.malloc(S * N * d * dt().itemsize + 256)
                 out = ctx.malloc(S * N * d * dt().itemsize + 256)
                 ctx.call(f"pgps_sample_normals_dev_{suf}", C.c_long(N), C.c_int(d), C.c_int(S), C.c_long(0), C.c_ulonglong(1),
@@ -88,7 +96,7 @@ def main():
                 t_draw = timed(ctx, lambda: run(None), args.reps, args.warmup)
                 t_z = timed(ctx, lambda: run(C.c_void_p(z)), args.reps, args.warmup)
                 isz = dt().itemsize
-                print(json.dumps({"d": d, "dtype": suf, "N": N, "S": S, "pkf_us": round(t_pkf, 1),
+                print(json.dumps({**({"label": args.label} if args.label else {}), "d": d, "dtype": suf, "N": N, "S": S, "pkf_us": round(t_pkf, 1),
                                   "sample_us": round(t_draw, 1), "sample_z_us": round(t_z, 1),
                                   "input_bytes_per_step_per_phase": (2 * d * d + d + d * d) * isz,
                                   "group_passes": 2 * -(-S // (8 if d <= 2 else 4 if d <= 4 else 2)),
