@@ -267,6 +267,31 @@ int pgps_pks_sample_dev_f32(pgps_ctx*, long N, int d, const float* Fs, const flo
 int pgps_sample_normals_dev_f64(pgps_ctx*, long N, int d, int S, long s0, unsigned long long seed, double* z);
 int pgps_sample_normals_dev_f32(pgps_ctx*, long N, int d, int S, long s0, unsigned long long seed, float* z);
 
+/* ---- joint posterior covariance between selected steps ----------------
+ * Cov(x_i, x_j | ys) = E_i E_{i+1} .. E_{j-1} sP_j for i < j, E_k the smoother gain of step k (the E of its smoothing
+ * element, from Fs, Qs and pgps_pkf_* output fPs) and sPs the pgps_pks_* output.  sel: n step indices, strictly
+ * increasing, 0 <= sel < N (else PGPS_E_INVALID); n = 1 is valid.  out: (n,n,d,d) blocks Cov(x_sel[a], x_sel[b]) if
+ * H == NULL, else (n,n) of H Cov H^T (H: d values, host memory); symmetric bit for bit.  d <= PGPS_MAX_DIM_LANE (else
+ * PGPS_E_UNSUPPORTED_DIM); an output that cannot be allocated returns PGPS_E_NOMEM.  float32 obeys pgps_set_f32_policy as
+ * pgps_pks_sample_f32 does.  _dev: every array but H is a device pointer (sel included). */
+int pgps_pks_cov_f64(pgps_ctx*, long N, int d, const double* Fs, const double* Qs, const double* fPs, const double* sPs,
+                     long n, const long* sel, const double* H, double* out);
+int pgps_pks_cov_f32(pgps_ctx*, long N, int d, const float* Fs, const float* Qs, const float* fPs, const float* sPs, long n,
+                     const long* sel, const float* H, float* out);
+int pgps_pks_cov_dev_f64(pgps_ctx*, long N, int d, const double* Fs, const double* Qs, const double* fPs,
+                         const double* sPs, long n, const long* sel, const double* H, double* out);
+int pgps_pks_cov_dev_f32(pgps_ctx*, long N, int d, const float* Fs, const float* Qs, const float* fPs, const float* sPs,
+                         long n, const long* sel, const float* H, float* out);
+/* its two passes on their own (native arithmetic of the type, device pointers): the gain products between consecutive
+ * selected steps, B (n-1,d,d), B_a = E_{sel[a]} .. E_{sel[a+1]-1} (a segmented scan over the N steps; n >= 2), and the
+ * fill of out from B and the n selected smoothed covariances sPsel (n,d,d) */
+int pgps_pks_cov_gains_dev_f64(pgps_ctx*, long N, int d, const double* Fs, const double* Qs, const double* fPs, long n,
+                               const long* sel, double* B);
+int pgps_pks_cov_gains_dev_f32(pgps_ctx*, long N, int d, const float* Fs, const float* Qs, const float* fPs, long n,
+                               const long* sel, float* B);
+int pgps_cov_fill_dev_f64(pgps_ctx*, long n, int d, const double* B, const double* sPsel, const double* H, double* out);
+int pgps_cov_fill_dev_f32(pgps_ctx*, long n, int d, const float* B, const float* sPsel, const float* H, float* out);
+
 /* ---- filter + smoother: pssgp/kalman/parallel.py:199-201 (pkfs) ------------------------
  * One fused three-launch pass.  Also returns the filtered moments and the log-likelihood
  * (the reference's pkfs drops them; StateSpaceGP runs the filter a second time for ll,
@@ -341,6 +366,17 @@ int pgps_lti_sample_f64(pgps_ctx*, long N, long K, int d, const double* F, const
 int pgps_lti_sample_dev_f64(pgps_ctx*, long N, long K, int d, const double* F, const double* Pinf, const double* H,
                             double R, const double* ts, const double* ys, double t0, const double* tq, int S, long s0,
                             unsigned long long seed, double* out, double* ll);
+
+/* model-level joint predictive, as pgps_lti_predict_*: merge sorted ts / tq, missing observations at the query rows,
+ * discretise, filter + smoother over the N + K steps, gain products between the query rows, fill.  mean (K) = H sm,
+ * cov (K,K) = H Cov(x_i, x_j) H^T of the queries, symmetric bit for bit, its diagonal the variances; ll (nullable) =
+ * training log-likelihood.  1 <= d <= PGPS_MAX_DIM_LANE, fp64. */
+int pgps_lti_predict_cov_f64(pgps_ctx*, long N, long K, int d, const double* F, const double* Pinf, const double* H,
+                             double R, const double* ts, const double* ys, double t0, const double* tq, double* mean,
+                             double* cov, double* ll);
+int pgps_lti_predict_cov_dev_f64(pgps_ctx*, long N, long K, int d, const double* F, const double* Pinf, const double* H,
+                                 double R, const double* ts, const double* ys, double t0, const double* tq, double* mean,
+                                 double* cov, double* ll);
 
 /* B models over the same series in one set of launches (hyper-parameter grids, HMC chains, multi-start optimisation
  * -- the realistic series, N = 1e3..1e5, are launch-latency bound one model at a time).  `models` is HOST memory,
@@ -499,6 +535,11 @@ int pgps_seq_ks_sample_f32(long N, int d, const float* Fs, const float* Qs, cons
                            long s0, unsigned long long seed, const float* z, const float* H, float* out);
 int pgps_seq_sample_normals_f64(long N, int d, int S, long s0, unsigned long long seed, double* z);
 int pgps_seq_sample_normals_f32(long N, int d, int S, long s0, unsigned long long seed, float* z);
+/* host twin of pgps_pks_cov_* (any d <= PGPS_MAX_DIM): the same definition, host pointers, no context */
+int pgps_seq_ks_cov_f64(long N, int d, const double* Fs, const double* Qs, const double* fPs, const double* sPs, long n,
+                        const long* sel, const double* H, double* out);
+int pgps_seq_ks_cov_f32(long N, int d, const float* Fs, const float* Qs, const float* fPs, const float* sPs, long n,
+                        const long* sel, const float* H, float* out);
 
 /* ---- host helper: the balancing sweep of balance_ss (pssgp/kernels/math_utils.py:10-29, numba in the reference) ----
  * scale[d] = accumulated diagonal scaling after n_iter sweeps over F (d,d).  Host pointers, no context. */

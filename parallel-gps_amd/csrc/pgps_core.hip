@@ -27,6 +27,7 @@ int ensure(pgps_ctx* ctx, DevBuf& b, size_t bytes) {
     hipError_t e = hipMalloc(&b.p, want);
     if (e != hipSuccess) {
         ctx->hip_err = std::string("hipMalloc: ") + hipGetErrorString(e);
+        (void)hipGetLastError();                    // reported here: the next call's launch check must not find it
         b.p = nullptr;
         return PGPS_E_NOMEM;
     }
@@ -2502,6 +2503,303 @@ extern "C" int pgps_lti_sample_dev_f64(pgps_ctx* c, long N, long K, int d, const
                                        const double* H, double R, const double* ts, const double* ys, double t0,
                                        const double* tq, int S, long s0, unsigned long long seed, double* out, double* ll) {
     return lti_sample_dev(c, N, K, d, F, Pinf, H, R, ts, ys, t0, tq, S, s0, seed, out, ll);
+}
+
+// ---------------------------------------------------------------------------------------------
+// joint posterior covariance between selected steps (pgps_cov.hip.h)
+// ---------------------------------------------------------------------------------------------
+namespace pgps {
+// bad <- 1 unless 0 <= sel[0] < sel[1] < .. < sel[n-1] < N
+static __global__ void k_cov_check(long N, long n, const long* sel, int* bad) {
+    for (long a = (long)blockIdx.x * blockDim.x + threadIdx.x; a < n; a += (long)gridDim.x * blockDim.x) {
+        const long k = sel[a];
+        if (k < 0 || k >= N || (a > 0 && sel[a - 1] >= k)) *bad = 1;
+    }
+}
+// slot[sel[a]] = a (slot filled with -1 before; sel checked before)
+static __global__ void k_cov_slots(long n, const long* sel, int* slot) {
+    for (long a = (long)blockIdx.x * blockDim.x + threadIdx.x; a < n; a += (long)gridDim.x * blockDim.x) slot[sel[a]] = (int)a;
+}
+// the selected steps' smoothed covariances, compact: sPsel[slot[k]] = sPs[k]; with sms: mean[slot[k]] = h . sms[k]
+template <typename T>
+static __global__ void k_cov_gather(long N, int d, long n, const int* slot, const T* sPs, T* sPsel, const T* sms, const T* h,
+                                    T* mean) {
+    const int dd = d * d;
+    for (long k = (long)blockIdx.x * blockDim.x + threadIdx.x; k < N; k += (long)gridDim.x * blockDim.x) {
+        const int a = slot[k];
+        if (a < 0 || a >= n) continue;
+        for (int i = 0; i < dd; ++i) sPsel[(long)a * dd + i] = sPs[k * dd + i];
+        if (sms) {
+            T acc = T(0);
+            for (int i = 0; i < d; ++i) acc += h[i] * sms[k * d + i];
+            mean[a] = acc;
+        }
+    }
+}
+}  // namespace pgps
+
+static dim3 cov_grid(long n) { return dim3((unsigned)std::max<long>(1, std::min<long>(4096, (n + 255) / 256))); }
+
+template <typename T>
+static int cov_gains_dispatch(pgps_ctx* ctx, int d, const CovArgs<T>& a) {
+    switch (d) {
+        case 1: return launch_cov_gains<T, 1>(ctx, a);
+        case 2: return launch_cov_gains<T, 2>(ctx, a);
+        case 3: return launch_cov_gains<T, 3>(ctx, a);
+        case 4: return launch_cov_gains<T, 4>(ctx, a);
+        case 5: return launch_cov_gains<T, 5>(ctx, a);
+        case 6: return launch_cov_gains<T, 6>(ctx, a);
+        default: return PGPS_E_UNSUPPORTED_DIM;
+    }
+}
+template <typename T>
+static int cov_fill_dispatch(pgps_ctx* ctx, int d, const CovFillArgs<T>& a) {
+    switch (d) {
+        case 1: return launch_cov_fill<T, 1>(ctx, a);
+        case 2: return launch_cov_fill<T, 2>(ctx, a);
+        case 3: return launch_cov_fill<T, 3>(ctx, a);
+        case 4: return launch_cov_fill<T, 4>(ctx, a);
+        case 5: return launch_cov_fill<T, 5>(ctx, a);
+        case 6: return launch_cov_fill<T, 6>(ctx, a);
+        default: return PGPS_E_UNSUPPORTED_DIM;
+    }
+}
+
+// bytes of the (n, n) or (n, n, d, d) output, 0 when no allocation could hold it
+static size_t cov_out_count(long n, int d, bool proj) {
+    const double cnt = (double)n * (double)n * (proj ? 1.0 : (double)d * d);
+    return cnt > 0x1p44 ? 0 : (size_t)n * (size_t)n * (proj ? 1 : (size_t)d * d);
+}
+
+// (n,) selection [device] -> ctx->cov[1] = (N,) slots; PGPS_E_INVALID unless strictly increasing inside [0, N)
+static int cov_slots(pgps_ctx* ctx, long N, long n, const long* sel, int** slot) {
+    int* bad;
+    TRY(stage_in<int>(ctx, ctx->cov[5], nullptr, 4, &bad));
+    TRY(stage_in<int>(ctx, ctx->cov[1], nullptr, (size_t)N, slot));
+    HIPCHK(ctx, hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(pgps::k_cov_check, cov_grid(n), dim3(256), 0, ctx->stream, N, n, sel, bad);
+    int bad_h = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&bad_h, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (bad_h) return PGPS_E_INVALID;
+    HIPCHK(ctx, hipMemsetAsync(*slot, 0xff, (size_t)N * sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(pgps::k_cov_slots, cov_grid(n), dim3(256), 0, ctx->stream, n, sel, *slot);
+    HIPCHK(ctx, hipGetLastError());
+    return PGPS_OK;
+}
+
+template <typename T>
+static int cov_gains_run(pgps_ctx* ctx, long N, int d, const T* Fs, const T* Qs, const T* fPs, long n, const int* slot, T* B) {
+    CovArgs<T> g{};
+    g.N = N; g.Fs = Fs; g.Qs = Qs; g.fPs = fPs; g.slot = slot; g.n = n; g.B = B;
+    return cov_gains_dispatch<T>(ctx, d, g);
+}
+template <typename T>
+static int cov_fill_run(pgps_ctx* ctx, long n, int d, const T* B, const T* sPsel, const T* H, T* out) {
+    CovFillArgs<T> f{};
+    f.n = n; f.B = B; f.sP = sPsel; f.proj = H ? 1 : 0; f.out = out;
+    for (int i = 0; i < d && H; ++i) f.h[i] = H[i];
+    return cov_fill_dispatch<T>(ctx, d, f);
+}
+
+// everything on the device but H: the selected sPs (and, with sms, the projected means) are gathered, then the two passes
+template <typename T>
+static int cov_core(pgps_ctx* ctx, long N, int d, const T* Fs, const T* Qs, const T* fPs, const T* sPs, long n, const int* slot,
+                    const T* H, T* out, const T* sms = nullptr, const T* h_dev = nullptr, T* mean = nullptr) {
+    const size_t dd = (size_t)d * d;
+    T *B, *sPsel;
+    TRY(stage_in<T>(ctx, ctx->cov[2], nullptr, (size_t)std::max<long>(1, n - 1) * dd, &B));
+    TRY(stage_in<T>(ctx, ctx->cov[3], nullptr, (size_t)n * dd, &sPsel));
+    hipLaunchKernelGGL(pgps::k_cov_gather<T>, cov_grid(N), dim3(256), 0, ctx->stream, N, d, n, slot, sPs, sPsel, sms, h_dev, mean);
+    HIPCHK(ctx, hipGetLastError());
+    if (n > 1) TRY(cov_gains_run<T>(ctx, N, d, Fs, Qs, fPs, n, slot, B));
+    return cov_fill_run<T>(ctx, n, d, B, sPsel, H, out);
+}
+
+// the float32 call in fp64 arithmetic: widened inputs, rounded output
+static int cov_run_wide(pgps_ctx* ctx, long N, int d, const float* Fs, const float* Qs, const float* fPs, const float* sPs,
+                        long n, const int* slot, const float* H, float* out, size_t nout) {
+    const size_t cnt = (size_t)N * d * d;
+    const int idx[4] = {2, 3, 6, 8};
+    const float* src[4] = {Fs, Qs, fPs, sPs};
+    pgps::ConvJobs cj{};
+    for (int i = 0; i < 4; ++i) {
+        TRY(ensure(ctx, ctx->wide[idx[i]], cnt * sizeof(double)));
+        cj.src[i] = src[i]; cj.dst[i] = ctx->wide[idx[i]].p; cj.n[i] = (long)cnt;
+    }
+    TRY(ensure(ctx, ctx->cov_wide, nout * sizeof(double)));
+    hipLaunchKernelGGL(pgps::k_widen_many, dim3((unsigned)std::min<size_t>(4096, (cnt + 255) / 256), 4u), dim3(256), 0,
+                       ctx->stream, cj);
+    double Hw[PGPS_MAX_DIM_LANE];
+    for (int i = 0; i < d && H; ++i) Hw[i] = (double)H[i];
+    double* ow = (double*)ctx->cov_wide.p;
+    TRY(cov_core<double>(ctx, N, d, (const double*)ctx->wide[2].p, (const double*)ctx->wide[3].p, (const double*)ctx->wide[6].p,
+                         (const double*)ctx->wide[8].p, n, slot, H ? Hw : nullptr, ow));
+    hipLaunchKernelGGL(pgps::k_narrow, dim3((unsigned)std::min<size_t>(4096, (nout + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (long)nout, (const double*)ow, out);
+    HIPCHK(ctx, hipGetLastError());
+    ctx->host_flags |= PGPS_STATUS_F32_PROMOTED;
+    return PGPS_OK;
+}
+
+template <typename T>
+static int pks_cov_dev(pgps_ctx* ctx, long N, int d, const T* Fs, const T* Qs, const T* fPs, const T* sPs, long n,
+                       const long* sel, const T* H, T* out) {
+    RoctxRange range_("parallel_covariance");
+    if (!ctx || N < 1 || N > 0x7fffffffL || n < 1 || n > N || !Fs || !Qs || !fPs || !sPs || !sel || !out) return PGPS_E_INVALID;
+    if (d < 1 || d > PGPS_MAX_DIM_LANE) return PGPS_E_UNSUPPORTED_DIM;
+    if (!aligned16(Fs) || !aligned16(Qs) || !aligned16(fPs) || !aligned16(sPs) || !aligned16(out) || (((uintptr_t)sel) & 7u))
+        return PGPS_E_INVALID;
+    const size_t nout = cov_out_count(n, d, H != nullptr);
+    if (!nout) return PGPS_E_NOMEM;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int* slot;
+    TRY(cov_slots(ctx, N, n, sel, &slot));
+    if constexpr (sizeof(T) == 4) {
+        // the policy of pgps_pks_f32: the dense-grid probe decides between the float32 kernels and the fp64 ones
+        int fixed = -1, nsamp = 0, dense = 0;
+        TRY(f32_probe_launch(ctx, N, d, Fs, &fixed, &nsamp));
+        if (fixed == 1) return cov_run_wide(ctx, N, d, Fs, Qs, fPs, sPs, n, slot, H, out, nout);
+        if (fixed != 0) {
+            TRY(f32_probe_result(ctx, nsamp, &dense));
+            ctx->f32_last_promoted = dense;
+            if (dense) return cov_run_wide(ctx, N, d, Fs, Qs, fPs, sPs, n, slot, H, out, nout);
+        }
+    }
+    return cov_core<T>(ctx, N, d, Fs, Qs, fPs, sPs, n, slot, H, out);
+}
+
+template <typename T>
+static int pks_cov_host(pgps_ctx* ctx, long N, int d, const T* Fs, const T* Qs, const T* fPs, const T* sPs, long n,
+                        const long* sel, const T* H, T* out) {
+    if (!ctx || N < 1 || n < 1 || n > N || !Fs || !Qs || !fPs || !sPs || !sel || !out) return PGPS_E_INVALID;
+    if (d < 1 || d > PGPS_MAX_DIM_LANE) return PGPS_E_UNSUPPORTED_DIM;
+    const size_t nout = cov_out_count(n, d, H != nullptr);
+    if (!nout) return PGPS_E_NOMEM;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t cnt = (size_t)N * d * d;
+    T *dFs, *dQs, *dfPs, *dsPs, *dout;
+    long* dsel;
+    TRY(stage_in<T>(ctx, ctx->st[8], nullptr, nout, &dout));        // the large one first: nothing is copied if it cannot be had
+    TRY(stage_in(ctx, ctx->st[1], Fs, cnt, &dFs));
+    TRY(stage_in(ctx, ctx->st[2], Qs, cnt, &dQs));
+    TRY(stage_in(ctx, ctx->st[6], fPs, cnt, &dfPs));
+    TRY(stage_in(ctx, ctx->st[7], sPs, cnt, &dsPs));
+    TRY(stage_in(ctx, ctx->st[3], sel, (size_t)n, &dsel));
+    TRY(pks_cov_dev<T>(ctx, N, d, dFs, dQs, dfPs, dsPs, n, dsel, H, dout));
+    TRY(stage_out(ctx, out, dout, nout));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PGPS_OK;
+}
+
+template <typename T>
+static int pks_cov_gains_dev(pgps_ctx* ctx, long N, int d, const T* Fs, const T* Qs, const T* fPs, long n, const long* sel,
+                             T* B) {
+    if (!ctx || N < 1 || N > 0x7fffffffL || n < 2 || n > N || !Fs || !Qs || !fPs || !sel || !B) return PGPS_E_INVALID;
+    if (d < 1 || d > PGPS_MAX_DIM_LANE) return PGPS_E_UNSUPPORTED_DIM;
+    if (!aligned16(Fs) || !aligned16(Qs) || !aligned16(fPs) || !aligned16(B) || (((uintptr_t)sel) & 7u)) return PGPS_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int* slot;
+    TRY(cov_slots(ctx, N, n, sel, &slot));
+    return cov_gains_run<T>(ctx, N, d, Fs, Qs, fPs, n, slot, B);
+}
+
+template <typename T>
+static int cov_fill_dev(pgps_ctx* ctx, long n, int d, const T* B, const T* sPsel, const T* H, T* out) {
+    if (!ctx || n < 1 || (n > 1 && !B) || !sPsel || !out) return PGPS_E_INVALID;
+    if (d < 1 || d > PGPS_MAX_DIM_LANE) return PGPS_E_UNSUPPORTED_DIM;
+    if (!aligned16(B) || !aligned16(sPsel) || !aligned16(out)) return PGPS_E_INVALID;
+    if (!cov_out_count(n, d, H != nullptr)) return PGPS_E_NOMEM;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return cov_fill_run<T>(ctx, n, d, B, sPsel, H, out);
+}
+
+#define PGPS_DEFINE_COV(SUF, T)                                                                                             \
+    extern "C" int pgps_pks_cov_##SUF(pgps_ctx* c, long N, int d, const T* Fs, const T* Qs, const T* fPs, const T* sPs,    \
+                                      long n, const long* sel, const T* H, T* out) {                                       \
+        return pks_cov_host<T>(c, N, d, Fs, Qs, fPs, sPs, n, sel, H, out);                                                 \
+    }                                                                                                                       \
+    extern "C" int pgps_pks_cov_dev_##SUF(pgps_ctx* c, long N, int d, const T* Fs, const T* Qs, const T* fPs,              \
+                                          const T* sPs, long n, const long* sel, const T* H, T* out) {                     \
+        return pks_cov_dev<T>(c, N, d, Fs, Qs, fPs, sPs, n, sel, H, out);                                                  \
+    }                                                                                                                       \
+    extern "C" int pgps_pks_cov_gains_dev_##SUF(pgps_ctx* c, long N, int d, const T* Fs, const T* Qs, const T* fPs,        \
+                                                long n, const long* sel, T* B) {                                           \
+        return pks_cov_gains_dev<T>(c, N, d, Fs, Qs, fPs, n, sel, B);                                                      \
+    }                                                                                                                       \
+    extern "C" int pgps_cov_fill_dev_##SUF(pgps_ctx* c, long n, int d, const T* B, const T* sPsel, const T* H, T* out) {   \
+        return cov_fill_dev<T>(c, n, d, B, sPsel, H, out);                                                                 \
+    }
+
+PGPS_DEFINE_COV(f64, double)
+PGPS_DEFINE_COV(f32, float)
+
+// the model-level joint predictive: merge (k_merge_sorted: its qslot is the position of a query row in the selection),
+// discretisation, filter + smoother over the N + K steps with the query rows missing, then the two passes between the
+// query rows
+static int lti_predict_cov_dev(pgps_ctx* ctx, long N, long K, int d, const double* F, const double* Pinf, const double* H,
+                               double R, const double* ts, const double* ys, double t0, const double* tq, double* mean,
+                               double* cov, double* ll) {
+    if (!ctx || N < 1 || K < 1 || !F || !Pinf || !H || !ts || !ys || !tq || !mean || !cov) return PGPS_E_INVALID;
+    if (d < 1 || d > PGPS_MAX_DIM_LANE) return PGPS_E_UNSUPPORTED_DIM;
+    if (N + K > 0x7fffffffL || !aligned16(cov)) return PGPS_E_INVALID;
+    if (!cov_out_count(K, d, true)) return PGPS_E_NOMEM;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t m = (size_t)(N + K), dd = (size_t)d * d;
+    double *tsm, *ysm, *model, *Fs, *Qs, *fms, *fPs, *sms, *sPs, *dll;
+    int* qslot;
+    TRY(stage_in<double>(ctx, ctx->lti[1], nullptr, m, &tsm));
+    TRY(stage_in<double>(ctx, ctx->lti[2], nullptr, m, &ysm));
+    TRY(stage_in<int>(ctx, ctx->lti[3], nullptr, m, &qslot));
+    TRY(launch_merge<double>(ctx, N, K, ts, ys, tq, tsm, ysm, qslot));
+    TRY(lti_model_in(ctx, d, F, Pinf, H, &model));
+    TRY(stage_in<double>(ctx, ctx->lti[4], nullptr, m * dd, &Fs));
+    TRY(stage_in<double>(ctx, ctx->lti[5], nullptr, m * dd, &Qs));
+    TRY(stage_in<double>(ctx, ctx->lti[6], nullptr, m * dd, &fPs));
+    TRY(stage_in<double>(ctx, ctx->lti[7], nullptr, m * d, &fms));
+    TRY(stage_in<double>(ctx, ctx->lti[8], nullptr, m * dd, &sPs));
+    TRY(stage_in<double>(ctx, ctx->lti[9], nullptr, m * d, &sms));
+    TRY(stage_in<double>(ctx, ctx->st[11], nullptr, 2, &dll));
+    TRY(disc_dev<double>(ctx, (long)m, d, model, model + dd, tsm, t0, Fs, Qs));
+    TRY(pkfs_dev<double>(ctx, (long)m, d, model + dd, Fs, Qs, model + 2 * dd, R, ysm, fms, fPs, sms, sPs, ll ? ll : dll));
+    return cov_core<double>(ctx, (long)m, d, Fs, Qs, fPs, sPs, K, qslot, H, cov, sms, model + 2 * dd, mean);
+}
+
+static int lti_predict_cov_host(pgps_ctx* ctx, long N, long K, int d, const double* F, const double* Pinf, const double* H,
+                                double R, const double* ts, const double* ys, double t0, const double* tq, double* mean,
+                                double* cov, double* ll) {
+    if (!ctx || N < 1 || K < 1 || !ts || !ys || !tq || !mean || !cov) return PGPS_E_INVALID;
+    const size_t nout = cov_out_count(K, d, true);
+    if (!nout) return PGPS_E_NOMEM;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    double *dts, *dys, *dtq, *dmean, *dcov, *dll;
+    TRY(stage_in<double>(ctx, ctx->st[8], nullptr, nout, &dcov));
+    TRY(stage_in(ctx, ctx->st[10], ts, (size_t)N, &dts));
+    TRY(stage_in(ctx, ctx->st[4], ys, (size_t)N, &dys));
+    TRY(stage_in(ctx, ctx->st[3], tq, (size_t)K, &dtq));
+    TRY(stage_in<double>(ctx, ctx->st[7], nullptr, (size_t)K, &dmean));
+    TRY(stage_in<double>(ctx, ctx->st[9], nullptr, 2, &dll));
+    TRY(lti_predict_cov_dev(ctx, N, K, d, F, Pinf, H, R, dts, dys, t0, dtq, dmean, dcov, dll));
+    TRY(stage_out(ctx, mean, dmean, (size_t)K));
+    TRY(stage_out(ctx, cov, dcov, nout));
+    double llh = 0.0;
+    TRY(stage_out(ctx, &llh, dll, 1));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (ll) *ll = llh;
+    return std::isfinite(llh) ? PGPS_OK : PGPS_E_NUMERIC;
+}
+
+extern "C" int pgps_lti_predict_cov_f64(pgps_ctx* c, long N, long K, int d, const double* F, const double* Pinf,
+                                        const double* H, double R, const double* ts, const double* ys, double t0,
+                                        const double* tq, double* mean, double* cov, double* ll) {
+    if (!F || !Pinf || !H) return PGPS_E_INVALID;
+    if (d < 1 || d > PGPS_MAX_DIM_LANE) return PGPS_E_UNSUPPORTED_DIM;
+    return lti_predict_cov_host(c, N, K, d, F, Pinf, H, R, ts, ys, t0, tq, mean, cov, ll);
+}
+extern "C" int pgps_lti_predict_cov_dev_f64(pgps_ctx* c, long N, long K, int d, const double* F, const double* Pinf,
+                                            const double* H, double R, const double* ts, const double* ys, double t0,
+                                            const double* tq, double* mean, double* cov, double* ll) {
+    return lti_predict_cov_dev(c, N, K, d, F, Pinf, H, R, ts, ys, t0, tq, mean, cov, ll);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -61,6 +61,8 @@ struct pgps_ctx {
     DevBuf wide[9];                     // fp64 copies of a promoted float32 call's arrays: P0, H, Fs, Qs, ys, fms, fPs, sms, sPs
     DevBuf smp;                         // backward sampler (pgps_sample.hip.h): lane suffixes and spine of every sample group
     DevBuf smp_wide;                    // ... a promoted float32 call's fp64 draws and output
+    DevBuf cov[6];                      // joint covariance (pgps_cov.hip.h): scan workspace, step slots, gain products, selected sPs, tile products, staged selection
+    DevBuf cov_wide;                    // ... a promoted float32 call's fp64 output
     void* comm = nullptr;               // ncclComm_t (RCCL) of a series sharded over GPUs: pgps_comm_init (pgps_comm.hip)
     int comm_rank = 0, comm_nranks = 0;
     DevBuf comm_buf;                    // [rec_f | rec_s | gathered_f | gathered_s] of pgps_pkfs_seg_dev_*
@@ -311,6 +313,42 @@ int launch_sample(pgps_ctx* ctx, SampleArgs<T> a);
 // z (S, N, d) = the library's draws of samples s0 .. s0 + S - 1 (any d)
 template <typename T>
 int launch_sample_normals(pgps_ctx* ctx, long N, int d, int S, long s0, unsigned long long seed, T* z);
+
+// Joint posterior covariance between selected steps (pgps_cov.hip.h): one (dtype, d) unit per
+// 1 <= d <= PGPS_MAX_DIM_LANE (pgps_cov_inst.hip).
+template <typename T>
+struct CovArgs {            // the gain products B_a = E_{sel[a]} .. E_{sel[a+1]-1}: a segmented scan over the N steps
+    long N;
+    const T* Fs;
+    const T* Qs;
+    const T* fPs;
+    const int* slot;        // (N,) position of step k in the selection, < 0 where it is not selected (k_merge_sorted's qslot)
+    long n;                 // selected steps
+    T* B;                   // (n - 1, d, d)
+    // launch geometry and workspace (filled by launch_cov_gains)
+    int Lc, nblocks;
+    long nlanes;
+    T* lsuf;                // (NREC, nlanes) field-major lane suffixes
+    T* spine;               // (nblocks, NREC)
+};
+constexpr int kCovTile = 64;    // rows of a fill tile = lanes of the wave that fills it
+template <typename T>
+struct CovFillArgs {        // out[a, b] = B_a .. B_{b-1} sP_b (a <= b), mirrored below the diagonal
+    long n;
+    const T* B;             // (n - 1, d, d)
+    const T* sP;            // (n, d, d) smoothed covariances of the selected steps
+    int proj;               // 1: out (n, n) = h^T Cov h, 0: out (n, n, d, d)
+    T h[PGPS_MAX_DIM_LANE];
+    T* out;
+    // workspace (filled by launch_cov_fill)
+    int nt;                 // row tiles, ceil(n / kCovTile)
+    T* U;                   // (n, d, d) U_j = B_{tT-1} .. B_{j-1}, t = j / T: carries column j to the row above its tile
+    T* M;                   // (nt, nt, d, d) M[s][t] = U_{(s+2)T-1} .. U_{tT-1}: from above tile t to the top row of tile s
+};
+template <typename T, int D>
+int launch_cov_gains(pgps_ctx* ctx, CovArgs<T> a);
+template <typename T, int D>
+int launch_cov_fill(pgps_ctx* ctx, CovFillArgs<T> a);
 
 // defined in pgps_inst.hip, one explicit instantiation per compiled (T, D)
 template <typename T, int D>

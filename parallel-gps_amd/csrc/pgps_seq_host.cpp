@@ -282,6 +282,76 @@ int seq_sample(long N, int d, const T* Fs, const T* Qs, const T* fms, const T* f
     return PGPS_OK;
 }
 
+// Joint covariance between selected steps, the definition of pgps_pks_cov_*: Cov(x_i, x_j | ys) =
+// E_i .. E_{j-1} sP_j for i < j, E_k = P_k F_{k+1}^T Pp_{k+1}^-1 the gain of step k's smoothing element.  First the products
+// B_a between consecutive selected steps, then column by column v <- B_{i-1} v from v = sym(sP_j) (H^T) upwards.
+template <typename T>
+int seq_cov(long N, int d, const T* Fs, const T* Qs, const T* fPs, const T* sPs, long n, const long* sel, const T* H, T* out) {
+    if (N < 1 || d < 1 || n < 1 || n > N || !Fs || !Qs || !fPs || !sPs || !sel || !out) return PGPS_E_INVALID;
+    if (d > PGPS_MAX_DIM) return PGPS_E_UNSUPPORTED_DIM;
+    for (long a = 0; a < n; ++a)
+        if (sel[a] < 0 || sel[a] >= N || (a > 0 && sel[a - 1] >= sel[a])) return PGPS_E_INVALID;
+    const size_t dd = (size_t)d * d;
+    Seq<T> w(d);
+    std::vector<T> B((size_t)(n - 1) * dd), E(dd), Pp(dd), A(dd), X(dd), acc(dd), tmp(dd);
+    for (long a = 0; a + 1 < n; ++a) {
+        for (size_t i = 0; i < dd; ++i) acc[i] = T(0);
+        for (int i = 0; i < d; ++i) acc[(size_t)i * d + i] = T(1);
+        for (long k = sel[a]; k < sel[a + 1]; ++k) {
+            w.predict(Fs + (k + 1) * dd, fPs + k * dd, Qs + (k + 1) * dd, Pp.data());      // Pp; w.FP = F P
+            for (size_t i = 0; i < dd; ++i) { A[i] = Pp[i]; X[i] = w.FP[i]; }
+            if (!lu_solve(d, A.data(), X.data())) return PGPS_E_NUMERIC;                    // X = Pp^-1 F P = E^T
+            for (int i = 0; i < d; ++i)
+                for (int j = 0; j < d; ++j) {
+                    T s = 0;
+                    for (int l = 0; l < d; ++l) s += acc[i * d + l] * X[j * d + l];
+                    tmp[i * d + j] = s;
+                }
+            acc = tmp;
+        }
+        for (size_t i = 0; i < dd; ++i) B[(size_t)a * dd + i] = acc[i];
+    }
+    const int W = H ? 1 : d;
+    std::vector<T> V((size_t)d * W), Vn((size_t)d * W);
+    for (long j = 0; j < n; ++j) {
+        const T* P = sPs + sel[j] * dd;
+        for (int i = 0; i < d; ++i) {
+            if (H) {
+                T s = 0;
+                for (int l = 0; l < d; ++l) s += T(0.5) * (P[i * d + l] + P[l * d + i]) * H[l];
+                V[i] = s;
+            } else {
+                for (int l = 0; l < d; ++l) V[(size_t)i * d + l] = T(0.5) * (P[i * d + l] + P[l * d + i]);
+            }
+        }
+        for (long i = j; i >= 0; --i) {
+            if (H) {
+                T c = 0;
+                for (int l = 0; l < d; ++l) c += H[l] * V[l];
+                out[(size_t)i * n + j] = c;
+                out[(size_t)j * n + i] = c;
+            } else {
+                for (int p = 0; p < d; ++p)
+                    for (int q = 0; q < d; ++q) {
+                        out[((size_t)i * n + j) * dd + p * d + q] = V[(size_t)p * d + q];
+                        out[((size_t)j * n + i) * dd + q * d + p] = V[(size_t)p * d + q];
+                    }
+            }
+            if (i > 0) {
+                const T* Bi = B.data() + (size_t)(i - 1) * dd;
+                for (int p = 0; p < d; ++p)
+                    for (int q = 0; q < W; ++q) {
+                        T s = 0;
+                        for (int l = 0; l < d; ++l) s += Bi[p * d + l] * V[(size_t)l * W + q];
+                        Vn[(size_t)p * W + q] = s;
+                    }
+                V = Vn;
+            }
+        }
+    }
+    return PGPS_OK;
+}
+
 template <typename T>
 int seq_normals(long N, int d, int S, long s0, unsigned long long seed, T* z) {
     if (N < 1 || d < 1 || S < 1 || s0 < 0 || s0 + S > 0xffffffffL || !z) return PGPS_E_INVALID;
@@ -357,4 +427,12 @@ extern "C" int pgps_seq_sample_normals_f64(long N, int d, int S, long s0, unsign
 }
 extern "C" int pgps_seq_sample_normals_f32(long N, int d, int S, long s0, unsigned long long seed, float* z) {
     return seq_normals<float>(N, d, S, s0, seed, z);
+}
+extern "C" int pgps_seq_ks_cov_f64(long N, int d, const double* Fs, const double* Qs, const double* fPs, const double* sPs,
+                                   long n, const long* sel, const double* H, double* out) {
+    return seq_cov<double>(N, d, Fs, Qs, fPs, sPs, n, sel, H, out);
+}
+extern "C" int pgps_seq_ks_cov_f32(long N, int d, const float* Fs, const float* Qs, const float* fPs, const float* sPs, long n,
+                                   const long* sel, const float* H, float* out) {
+    return seq_cov<float>(N, d, Fs, Qs, fPs, sPs, n, sel, H, out);
 }

@@ -116,6 +116,15 @@ def _declare(lib):
     for dev in ("", "_dev"):
         getattr(lib, f"pgps_lti_sample{dev}_f64").argtypes = [P, c_long, c_long, c_int, P, P, P, c_double, P, P, c_double, P,
                                                              c_int, c_long, u64, P, P]
+    for suf in ("f64", "f32"):
+        for dev in ("", "_dev"):
+            getattr(lib, f"pgps_pks_cov{dev}_{suf}").argtypes = [P, c_long, c_int, P, P, P, P, c_long, P, P, P]
+        getattr(lib, f"pgps_pks_cov_gains_dev_{suf}").argtypes = [P, c_long, c_int, P, P, P, c_long, P, P]
+        getattr(lib, f"pgps_cov_fill_dev_{suf}").argtypes = [P, c_long, c_int, P, P, P, P]
+        getattr(lib, f"pgps_seq_ks_cov_{suf}").argtypes = [c_long, c_int, P, P, P, P, c_long, P, P, P]
+    for dev in ("", "_dev"):
+        getattr(lib, f"pgps_lti_predict_cov{dev}_f64").argtypes = [P, c_long, c_long, c_int, P, P, P, c_double, P, P, c_double,
+                                                                  P, P, P, P]
     return lib
 
 
@@ -539,6 +548,55 @@ def lti_sample(F, Pinf, H, R, ts, ys, tq, num_samples, seed, t0=0.0, first_sampl
                              c_double(float(R)), _ptr(ts_a), _ptr(ys_a), c_double(float(t0)), _ptr(tq_a), c_int(S),
                              c_long(int(first_sample)), ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)), _ptr(out), None)
     return out
+
+
+def _cov_inputs(lgssm, Ps, sPs, steps, H):
+    dtype = _dtype_of(lgssm)
+    _, Fs, Qs, *_ = lgssm
+    Fs = _prep(Fs, dtype)
+    N, d = Fs.shape[0], Fs.shape[1]
+    sel = np.ascontiguousarray(np.asarray(steps).reshape(-1), dtype=np.int64)
+    n = sel.shape[0]
+    if n < 1 or sel[0] < 0 or sel[-1] >= N or np.any(np.diff(sel) <= 0):
+        raise ValueError(f"steps must be a non-empty, strictly increasing selection of 0..{N - 1}")
+    H = None if H is None else _prep(H, dtype, (d,))
+    out = np.empty((n, n) if H is not None else (n, n, d, d), dtype)
+    return dtype, N, d, n, Fs, _prep(Qs, dtype, (N, d, d)), _prep(Ps, dtype, (N, d, d)), _prep(sPs, dtype, (N, d, d)), sel, H, out
+
+
+def pks_cov(lgssm, Ps, sPs, steps, H=None, device=0):
+    """Joint posterior covariance of the states at the selected `steps` (strictly increasing indices) on the GPU
+    (pgps_pks_cov_*): Fs, Qs of `lgssm`, the filtered covariances Ps (N, d, d) and the smoothed ones sPs (N, d, d) ->
+    (n, n, d, d) blocks out[a, b] = Cov(x_steps[a], x_steps[b] | ys), or (n, n) of H Cov H^T when H (d,) is given.  The
+    products of the smoother gains between consecutive selected steps by a segmented scan, then the fill: no dense
+    algebra over the N steps.  d <= 6 (larger: PgpsError, PGPS_E_UNSUPPORTED_DIM); the host twin is sequential.ks_cov."""
+    dtype, N, d, n, Fs, Qs, Ps, sPs, sel, H, out = _cov_inputs(lgssm, Ps, sPs, steps, H)
+    suf, _ = _suffix(dtype)
+    get_context(device).call(f"pgps_pks_cov_{suf}", c_long(N), c_int(d), _ptr(Fs), _ptr(Qs), _ptr(Ps), _ptr(sPs), c_long(n),
+                             _ptr(sel), _ptr(H), _ptr(out))
+    return out
+
+
+def lti_predict_cov(F, Pinf, H, R, ts, ys, tq, t0=0.0, device=0):
+    """predict_f(full_cov=True) of any LTI state-space GP with d <= 6 on the device (pgps_lti_predict_cov_f64): merge of
+    the sorted `ts` (N) and `tq` (K), discretisation, filter + smoother over the N + K steps, gain products between the
+    query rows, fill.  Returns (mean (K,), cov (K, K) symmetric bit for bit, ll of the training series).  Larger d raises
+    PgpsError (PGPS_E_UNSUPPORTED_DIM)."""
+    F = _prep(F, np.float64)
+    d = F.shape[0]
+    Pinf, H = _prep(Pinf, np.float64, (d, d)), _prep(H, np.float64, (d,))
+    ts_a = _prep(ts, np.float64, (-1,))
+    ys_a = _prep(ys, np.float64, (-1,))
+    tq_a = _prep(tq, np.float64, (-1,))
+    N, K = ts_a.shape[0], tq_a.shape[0]
+    if ys_a.shape[0] != N:
+        raise ValueError(f"observations has {ys_a.shape[0]} rows, the series {N} steps")
+    mean, cov = np.empty(K, np.float64), np.empty((K, K), np.float64)
+    ll = c_double(0.0)
+    get_context(device).call("pgps_lti_predict_cov_f64", c_long(N), c_long(K), c_int(d), _ptr(F), _ptr(Pinf), _ptr(H),
+                             c_double(float(R)), _ptr(ts_a), _ptr(ys_a), c_double(float(t0)), _ptr(tq_a), _ptr(mean),
+                             _ptr(cov), ctypes.cast(ctypes.byref(ll), c_void_p))
+    return mean, cov, ll.value
 
 
 def pkfs(lgssm, observations, return_filtered=False, return_loglikelihood=False, device=0):

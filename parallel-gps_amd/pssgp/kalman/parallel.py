@@ -7,7 +7,7 @@ accepted and ignored: the reference needs it to bound the depth of tfp's recursi
 """
 from .. import _backend
 
-__all__ = ["pkf", "pks", "pkfs", "pks_sample"]
+__all__ = ["pkf", "pks", "pkfs", "pks_sample", "pks_cov"]
 
 
 def pkf(lgssm, observations, return_loglikelihood=False, max_parallel=10000):
@@ -33,3 +33,10 @@ def pks_sample(lgssm, ms, Ps, num_samples=1, seed=0, first_sample=0, z=None):
     on the GPU.  z (S, N, d): standard normals to use; None = the library's draws of samples
     first_sample .. first_sample + S - 1 under `seed` (sequential.ks_sample draws the same)."""
     return _backend.pks_sample(lgssm, ms, Ps, num_samples, seed, first_sample=first_sample, z=z)
+
+
+def pks_cov(lgssm, Ps, sPs, steps, H=None):
+    """Joint posterior covariance of the states at the selected steps, from the filtered covariances Ps and the smoothed
+    ones sPs, on the GPU: (n, n, d, d), or (n, n) of H Cov H^T when H is given.  sequential.ks_cov is
+    the host twin."""
+    return _backend.pks_cov(lgssm, Ps, sPs, steps, H=H)

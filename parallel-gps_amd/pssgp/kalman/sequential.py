@@ -10,7 +10,7 @@ import numpy as np
 
 from .. import _backend
 
-__all__ = ["kf", "ks", "kfs", "ks_sample", "sample_normals"]
+__all__ = ["kf", "ks", "kfs", "ks_sample", "sample_normals", "ks_cov"]
 
 
 def _ptr(a):
@@ -81,6 +81,18 @@ def ks_sample(lgssm, ms, Ps, num_samples=1, seed=0, first_sample=0, z=None, H=No
     code = getattr(lib, f"pgps_seq_ks_sample_{suf}")(N, d, _ptr(Fs), _ptr(Qs), _ptr(ms), _ptr(Ps), S, int(first_sample),
                                                      int(seed) & (2 ** 64 - 1), _ptr(z), _ptr(H), _ptr(out))
     _backend.check(None, code, "pgps_seq_ks_sample")
+    return out
+
+
+def ks_cov(lgssm, Ps, sPs, steps, H=None):
+    """Host twin of parallel.pks_cov (pgps_seq_ks_cov_*): the same definition, any d.  (n, n, d, d), or (n, n) of
+    H Cov H^T when H is given."""
+    lib = _backend.load_library()
+    dtype, N, d, n, Fs, Qs, Ps, sPs, sel, H, out = _backend._cov_inputs(lgssm, Ps, sPs, steps, H)
+    suf, _ = _backend._suffix(dtype)
+    code = getattr(lib, f"pgps_seq_ks_cov_{suf}")(N, d, _ptr(Fs), _ptr(Qs), _ptr(Ps), _ptr(sPs), n, _ptr(sel), _ptr(H),
+                                                  _ptr(out))
+    _backend.check(None, code, "pgps_seq_ks_cov")
     return out
 
 

@@ -74,6 +74,25 @@ def _public_evaluation(fn):
     return wrapper
 
 
+def _host_discretise(F, P0, ts, t0=0.0):
+    """Fs[k] = expm(dt_k F), Qs[k] = sym(P0 - Fs[k] P0 Fs[k]^T) on the host in fp64 (P0 stationary), dts = diff([t0; ts]):
+    what _backend.discretise computes on the device, for the evaluations that stay on the host throughout."""
+    from scipy.linalg import expm
+    F, P0 = np.asarray(F, np.float64), np.asarray(P0, np.float64)
+    dts = np.diff(np.concatenate([[float(t0)], np.asarray(ts, np.float64).reshape(-1)]))
+    d = F.shape[0]
+    Fs, Qs = np.empty((dts.size, d, d)), np.empty((dts.size, d, d))
+    seen = {}
+    for k, dt in enumerate(dts):
+        hit = seen.get(dt)
+        if hit is None:
+            Fk = expm(dt * F)
+            Qk = P0 - Fk @ P0 @ Fk.T
+            hit = seen[dt] = (Fk, 0.5 * (Qk + Qk.T))
+        Fs[k], Qs[k] = hit
+    return Fs, Qs
+
+
 class StateSpaceGP:
     def __init__(self, data, kernel, noise_variance=1.0, parallel=False, max_parallel=10000):
         self.noise_variance = float(noise_variance)
@@ -355,7 +374,10 @@ class StateSpaceGP:
     def predict_f(self, Xnew, full_cov=False, full_output_cov=False):
         """Posterior mean (K, 1) and variance (K, 1) at `Xnew` (pssgp/model.py:92-111):
         merge train and query times, mark queries as missing, smooth, keep the query rows,
-        project through H."""
+        project through H.  full_cov=True: the mean (K, 1) and the joint posterior covariance (1, K, K) of f(Xnew)
+        (GPflow's [num_latent, K, K]; _predict_f_full_cov) -- the law of predict_f_samples' draws."""
+        if full_cov:
+            return self._predict_f_full_cov(Xnew)
         ts, ys = self.data
         dtype = config.default_float()
         Xnew = np.asarray(Xnew, dtype=dtype)
@@ -417,6 +439,43 @@ class StateSpaceGP:
         var = np.einsum("ai,nij,aj->na", H, sP, H)
         return mean, var
 
+    def _predict_f_full_cov(self, Xnew):
+        """predict_f(Xnew, full_cov=True): mean (K, 1) and covariance (1, K, K), symmetric bit for bit, its diagonal the
+        variances.  Cov(x_i, x_j | ys) = E_i .. E_{j-1} sP_j between query rows i < j of the merged series (E the smoother
+        gains): no dense algebra over the training points.  parallel=True: merge, discretisation, filter +
+        smoother, the products of the gains between the query rows and the fill on the device for any kernel with d <= 6
+        (pgps_lti_predict_cov_f64; larger d raises PgpsError); parallel=False: discretisation (_host_discretise), filter +
+        smoother and sequential.ks_cov on the host, any d, no device needed.  Computed in fp64 and rounded to the default float.  Any order of Xnew; equal query
+        times give equal rows and columns."""
+        dtype = config.default_float()
+        xq = np.asarray(Xnew, dtype=np.float64).reshape(-1)
+        if xq.size == 0:
+            return np.zeros((0, 1), dtype), np.zeros((1, 0, 0), dtype)
+        tq, inverse = np.unique(xq, return_inverse=True)          # sorted, each time once
+        ts, ys = self.data
+        squeezed_ts = np.asarray(ts, np.float64).reshape(-1)
+        if self.parallel:
+            from . import _backend
+            sde = self.kernel.get_sde()
+            mean, cov, ll = _backend.lti_predict_cov(sde.F, sde.P0, sde.H, self.noise_variance, squeezed_ts,
+                                                     np.asarray(ys, np.float64).reshape(-1), tq)
+        else:
+            nan_ys = np.full((tq.shape[0], ys.shape[1]), np.nan, dtype=np.float64)
+            all_ts, all_ys, all_flags = _merge_sorted(
+                squeezed_ts, tq, (np.asarray(ys, np.float64), nan_ys),
+                (np.zeros(squeezed_ts.shape, dtype=bool), np.ones(tq.shape, dtype=bool)))
+            sde = self.kernel.get_sde()
+            h = np.asarray(sde.H, np.float64).reshape(-1)
+            P0 = np.asarray(sde.P0, np.float64)
+            Fs, Qs = _host_discretise(sde.F, P0, all_ts)
+            ssm = (P0, Fs, Qs, h[None, :], np.reshape(np.float64(self.noise_variance), (1, 1)))
+            fms, fPs, mps, Pps = kf(ssm, all_ys, return_predicted=True)
+            sms, sPs = sequential.ks(ssm, fms, fPs, mps, Pps)
+            rows = np.flatnonzero(all_flags)
+            mean = sms[rows] @ h
+            cov = sequential.ks_cov(ssm, fPs, sPs, rows, H=h)
+        return mean[inverse][:, None].astype(dtype), cov[np.ix_(inverse, inverse)][None].astype(dtype)
+
     @_public_evaluation
     def predict_f_samples(self, Xnew, num_samples=None, full_cov=True, full_output_cov=False, seed=None):
         """Joint posterior draws of f at `Xnew` (GPflow's predict_f_samples): (S, K, 1), or (K, 1) when num_samples is
@@ -424,7 +483,8 @@ class StateSpaceGP:
         with d <= 6 (pgps_lti_sample_f64; larger d raises PgpsError); parallel=False: the host filter and its
         backward-sampling twin, any d.  Both use the library's draws under `seed` (None: a fresh 64-bit seed per call), so
         the two modes give the same samples at the same seed.  full_cov=False: independent draws from predict_f's
-        marginals.  Any order of Xnew; equal query times get equal values."""
+        marginals.  Any order of Xnew; equal query times get equal values.  The law of the joint draws is
+        N(mean, cov) of predict_f(Xnew, full_cov=True), which the library returns without Monte Carlo."""
         del full_output_cov                 # (single output)
         dtype = config.default_float()
         S = 1 if num_samples is None else int(num_samples)
