@@ -423,6 +423,48 @@ int pgps_gp_ll_batch_dev_f64(pgps_ctx*, int B, long N, int d, const double* mode
 int pgps_gp_ll_batch_dev_f32(pgps_ctx*, int B, long N, int d, const double* models, const float* ts, double t0,
                              const float* ys, double* ll);
 
+/* ---- predict_f at B hyper-parameter settings (fused path, d <= 3) --------------------------------
+ * The posterior of f at K query times for B models over the SAME series and the SAME query grid in one set of launches:
+ * one merge (shared), then B filters + smoothers + projections side by side -- the last step of the reference's MCMC
+ * drivers (pssgp/experiments/sunspot/mcmc.py:78-97: predict_f at the draws of the chain), one launch-latency-bound call
+ * per draw otherwise.  `models` (HOST memory) as pgps_gp_ll_batch_*: B blocks [lam | N1 | N2 | Pinf | H | R]; ts (N), tq (K)
+ * sorted, ties merged as in pgps_gp_predict_*; mean, var: (B, K) row-major; ll: B training log-likelihoods or NULL.
+ * Host pointers; device pointers (except models) for the _dev forms, which return with the launches enqueued (they
+ * synchronise the stream ONCE, before the launches, to copy the model table in).  Row b equals
+ * pgps_gp_predict_* of model b up to rounding (another bracketing of the same scans), and does not depend on the other
+ * rows, on its position, on B's split into groups (pgps_set_batch_scratch) -- the geometry is fixed per call from
+ * (B, N + K).  Errors: B, N, K < 1, a null pointer, lam <= 0 or R <= 0 in a row: PGPS_E_INVALID; d outside 1..3:
+ * PGPS_E_UNSUPPORTED_DIM; a non-finite log-likelihood (host forms): PGPS_E_NUMERIC; no scratch: PGPS_E_NOMEM. */
+int pgps_gp_predict_batch_f64(pgps_ctx*, int B, long N, long K, int d, const double* models, const double* ts,
+                              const double* ys, double t0, const double* tq, double* mean, double* var, double* ll);
+int pgps_gp_predict_batch_f32(pgps_ctx*, int B, long N, long K, int d, const double* models, const float* ts,
+                              const float* ys, double t0, const float* tq, float* mean, float* var, double* ll);
+int pgps_gp_predict_batch_dev_f64(pgps_ctx*, int B, long N, long K, int d, const double* models, const double* ts,
+                                  const double* ys, double t0, const double* tq, double* mean, double* var, double* ll);
+int pgps_gp_predict_batch_dev_f32(pgps_ctx*, int B, long N, long K, int d, const double* models, const float* ts,
+                                  const float* ys, double t0, const float* tq, float* mean, float* var, double* ll);
+/* The same for ANY kernel's LTI model (fp64, 2 <= d <= 16; d outside: PGPS_E_UNSUPPORTED_DIM): `models` (HOST) as
+ * pgps_lti_ll_batch_*, B rows [F | Pinf | H | R].  One merge, one batched discretisation, then the row-cooperative filter +
+ * smoother + projection of all models side by side (one model per blockIdx.y): the launches of ONE predict whatever B,
+ * in groups that fit the batch budget (default 1 GiB here; about 3 (N + K) d^2 doubles per model).  The chain length is
+ * fixed per call from (B, N + K), so a row does not depend on the grouping, on its position or on the other rows. */
+int pgps_lti_predict_batch_f64(pgps_ctx*, int B, long N, long K, int d, const double* models, const double* ts,
+                               const double* ys, double t0, const double* tq, double* mean, double* var, double* ll);
+int pgps_lti_predict_batch_dev_f64(pgps_ctx*, int B, long N, long K, int d, const double* models, const double* ts,
+                                   const double* ys, double t0, const double* tq, double* mean, double* var, double* ll);
+/* Moments of the mixture sum_b w_b N(mean_b, var_b), column by column of (B, K) device arrays: mean_out = sum_b w_b mean_b,
+ * var_out = sum_b w_b (var_b + (mean_b - mean_out)^2) -- two passes, every term non-negative; w (B, device) is used as
+ * given (normalise it), NULL = 1 / B each.  fp64, deterministic (fixed summation order).  Does not synchronise. */
+int pgps_mix_moments_dev_f64(pgps_ctx*, int B, long K, const double* mean, const double* var, const double* w,
+                             double* mean_out /* K */, double* var_out /* K */);
+/* Scratch budget of the batched predict in bytes (0 = the defaults: 64 MiB for pgps_gp_predict_batch_*, 1 GiB for
+ * pgps_lti_predict_batch_*): the models run in groups whose filtered
+ * moments and scan records fit it (one model at least).  Results do not depend on it. */
+int pgps_set_batch_scratch(pgps_ctx* ctx, size_t bytes);
+/* Launch form of pgps_gp_predict_batch_*: 0 = automatic (form 2), 1 = one workgroup per model in one launch (taken up to
+ * 65 536 merged steps, form 2 beyond), 2 = three launches of (workgroups, models) grids. */
+int pgps_set_batch_form(pgps_ctx* ctx, int form);
+
 /* ---- log-likelihood and its gradient (fused path, d <= 3, fp64) --------------------------------
  * What the reference gets from TensorFlow autodiff through the scan (tests/test_gp_vs_kfs.py:53-78;
  * SURVEY.md section 8f, rank 1): forward-mode dual numbers carried through every filtering element and
@@ -564,6 +606,13 @@ int pgps_series_gp_ll_f64(pgps_series* s, int d, double lam, const double* N1, c
 int pgps_series_gp_ll_grad_f64(pgps_series* s, int d, int np, const double* model, double* out /* 1 + np */);
 int pgps_series_gp_predict_f64(pgps_series* s, int d, double lam, const double* N1, const double* N2, const double* Pinf,
                                const double* H, double R, double* mean /* K */, double* var /* K */, double* ll /* or NULL */);
+/* pgps_gp_predict_batch_f64 on a resident series with its query grid set (pgps_series_set_queries_f64).  w == NULL: mean, var receive
+ * (B, K); w = B mixture weights (host, used as given): the (B, K) results stay on the device and mean, var receive the K
+ * moments of the mixture (pgps_mix_moments_dev_f64). */
+int pgps_series_gp_predict_batch_f64(pgps_series* s, int B, int d, const double* models, const double* w, double* mean,
+                                     double* var, double* ll /* B, or NULL */);
+int pgps_series_lti_predict_batch_f64(pgps_series* s, int B, int d, const double* models /* [F | Pinf | H | R] */, const double* w,
+                                      double* mean, double* var, double* ll /* B, or NULL */);
 /* Log-likelihood and the ADJOINTS of the fused model by one filter pass and one reverse pass (csrc/pgps_gpadj.hip.h; the
  * lane-chunk twin of pgps_lti_ll_grad_*): out = [ll | Abar (d d, row-major) | Ubar (d) | Hbar (d) | Rbar], 1 + d d + 2 d + 1
  * doubles, with  d ll / d theta = <Abar, dF> + Ubar^T dPinf H^T + Hbar . dH + Rbar dR  for every dF that commutes with F -- for

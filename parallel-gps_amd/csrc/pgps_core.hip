@@ -100,6 +100,7 @@ extern "C" int pgps_destroy(pgps_ctx* ctx) {
     if (ctx->gadj.p) (void)hipFree(ctx->gadj.p);
     if (ctx->pin_d.p) (void)hipFree(ctx->pin_d.p);
     if (ctx->pin_h) (void)hipHostFree(ctx->pin_h);
+    if (ctx->out_h) (void)hipHostFree(ctx->out_h);
     if (ctx->status_word) (void)hipFree(ctx->status_word);
     for (auto& b : ctx->st)
         if (b.p) (void)hipFree(b.p);
@@ -1668,8 +1669,12 @@ static void series_free_queries(pgps_series* s) {
 static int series_host(pgps_series* s, size_t doubles) {
     if (s->host_cap >= doubles) return PGPS_OK;
     if (s->host) (void)hipHostFree(s->host);
-    s->host = nullptr; s->host_cap = 0;
-    if (hipHostMalloc((void**)&s->host, doubles * sizeof(double), hipHostMallocDefault) != hipSuccess) return PGPS_E_NOMEM;
+    s->host = nullptr; s->host_cap = 0; s->hdev = nullptr;
+    if (hipHostMalloc((void**)&s->host, doubles * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+        s->host = nullptr;
+        (void)hipGetLastError();                    // reported here: the next call's launch check must not find it
+        return PGPS_E_NOMEM;
+    }
     s->host_cap = doubles;
     const char* env = std::getenv("PGPS_SERIES_ZERO_COPY");
     s->zero_copy = !(env && env[0] == '0');
@@ -2805,15 +2810,10 @@ extern "C" int pgps_lti_predict_cov_dev_f64(pgps_ctx* c, long N, long K, int d, 
 // ---------------------------------------------------------------------------------------------
 // batched log-likelihood: B hyper-parameter settings over one series
 // ---------------------------------------------------------------------------------------------
-template <typename T>
-static int gp_ll_batch_dev(pgps_ctx* ctx, int B, long N, int d, const double* models_host, const T* ts, double t0,
-                           const T* ys, double* ll) {
-    if (!ctx || B < 1 || B > 65535 || N < 1 || !models_host || !ts || !ys || !ll) return PGPS_E_INVALID;
-    if (d < 1 || d > 3) return PGPS_E_UNSUPPORTED_DIM;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    // models: B blocks [lam | N1 (d*d) | N2 (d*d) | Pinf (d*d) | H (d) | R] from the caller, re-packed
-    // to the fixed device stride
-    std::vector<double> packed((size_t)B * kGpModelStride, 0.0);
+// models: B blocks [lam | N1 (d*d) | N2 (d*d) | Pinf (d*d) | H (d) | R] from the caller, re-packed to the fixed device
+// stride (kGpModelStride); lam <= 0 or R <= 0 in any row: PGPS_E_INVALID
+static int gp_pack_models(int B, int d, const double* models_host, std::vector<double>& packed) {
+    packed.assign((size_t)B * kGpModelStride, 0.0);
     const int in_stride = 1 + 3 * d * d + d + 1;
     for (int m = 0; m < B; ++m) {
         const double* p = models_host + (size_t)m * in_stride;
@@ -2824,6 +2824,17 @@ static int gp_ll_batch_dev(pgps_ctx* ctx, int B, long N, int d, const double* mo
         q[31] = p[1 + 3 * d * d + d];
         if (!(q[0] > 0.0) || !(q[31] > 0.0)) return PGPS_E_INVALID;
     }
+    return PGPS_OK;
+}
+
+template <typename T>
+static int gp_ll_batch_dev(pgps_ctx* ctx, int B, long N, int d, const double* models_host, const T* ts, double t0,
+                           const T* ys, double* ll) {
+    if (!ctx || B < 1 || B > 65535 || N < 1 || !models_host || !ts || !ys || !ll) return PGPS_E_INVALID;
+    if (d < 1 || d > 3) return PGPS_E_UNSUPPORTED_DIM;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::vector<double> packed;
+    TRY(gp_pack_models(B, d, models_host, packed));
     double* dmodels;
     TRY(stage_in<double>(ctx, ctx->st[0], nullptr, packed.size(), &dmodels));
     // the packed vector dies with this frame: synchronous copy (pageable memory, so hipMemcpyAsync would
@@ -2872,6 +2883,373 @@ static int gp_ll_batch_host(pgps_ctx* ctx, int B, long N, int d, const double* m
 
 PGPS_DEFINE_LL_BATCH(f64, double)
 PGPS_DEFINE_LL_BATCH(f32, float)
+
+// ---------------------------------------------------------------------------------------------
+// batched predict_f: B hyper-parameter settings over one series and one query grid (fused path, d <= 3)
+// ---------------------------------------------------------------------------------------------
+extern "C" int pgps_set_batch_scratch(pgps_ctx* ctx, size_t bytes) {
+    if (!ctx) return PGPS_E_INVALID;
+    ctx->batch_scratch = bytes;
+    return PGPS_OK;
+}
+extern "C" int pgps_set_batch_form(pgps_ctx* ctx, int form) {
+    if (!ctx || form < 0 || form > 2) return PGPS_E_INVALID;
+    ctx->batch_form = form;
+    return PGPS_OK;
+}
+
+// Device results -> pageable host arrays through a pinned buffer of the context (kept, grown on demand) and a memcpy: an
+// asynchronous copy straight into pageable memory pins the destination's pages on its way (measured on predict_f_batch:
+// 3.2 MB of results took 19 ms of a 20 ms call that way).  Synchronises the stream.  Above kOutPinnedMax, or when the
+// pinned allocation fails, the parts are copied directly.
+constexpr size_t kOutPinnedMax = (size_t)1 << 30;
+struct OutPart { void* host; const void* dev; size_t bytes; };
+static int copy_out(pgps_ctx* ctx, const OutPart* parts, int n) {
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) total += (parts[i].bytes + 255) / 256 * 256;
+    if (total <= kOutPinnedMax && total > ctx->out_cap) {
+        if (ctx->out_h) (void)hipHostFree(ctx->out_h);
+        ctx->out_h = nullptr;
+        ctx->out_cap = 0;
+        if (hipHostMalloc((void**)&ctx->out_h, total + total / 8, hipHostMallocDefault) == hipSuccess) ctx->out_cap = total + total / 8;
+        else { ctx->out_h = nullptr; (void)hipGetLastError(); }
+    }
+    const bool pinned = total <= ctx->out_cap;
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        void* dst = pinned ? (void*)(ctx->out_h + off) : parts[i].host;
+        HIPCHK(ctx, hipMemcpyAsync(dst, parts[i].dev, parts[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+        off += (parts[i].bytes + 255) / 256 * 256;
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (pinned) {
+        off = 0;
+        for (int i = 0; i < n; ++i) {
+            std::memcpy(parts[i].host, ctx->out_h + off, parts[i].bytes);
+            off += (parts[i].bytes + 255) / 256 * 256;
+        }
+    }
+    return PGPS_OK;
+}
+
+// the B models over an ALREADY MERGED series of m steps (ts_m, ys_m, qslot on the device); mean, var (B, K), ll (B) device
+template <typename T>
+static int gp_predict_batch_merged(pgps_ctx* ctx, int B, size_t m, long K, int d, const double* models_host, const T* ts_m,
+                                   const T* ys_m, double t0, const int* qslot, T* mean, T* var, double* ll) {
+    std::vector<double> packed;
+    TRY(gp_pack_models(B, d, models_host, packed));
+    double* dmodels;
+    TRY(stage_in<double>(ctx, ctx->st[5], nullptr, packed.size(), &dmodels));
+    // the packed vector dies with this frame: synchronous copy, as in gp_ll_batch_dev
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpy(dmodels, packed.data(), packed.size() * sizeof(double), hipMemcpyHostToDevice));
+    GpBatchArgs<T> b{};
+    b.N = (long)m;
+    b.ts = ts_m;
+    b.ys = ys_m;
+    b.t_prev = (T)t0;
+    b.models = dmodels;
+    b.ll = ll;
+    b.qslot = qslot;
+    b.pmean = mean;
+    b.pvar = var;
+    b.K = K;
+    RoctxRange range_("parallel_filter");
+    switch (d) {
+        case 1: return launch_gp_predict_batch<T, 1>(ctx, B, b);
+        case 2: return launch_gp_predict_batch<T, 2>(ctx, B, b);
+        default: return launch_gp_predict_batch<T, 3>(ctx, B, b);
+    }
+}
+
+template <typename T>
+static int gp_predict_batch_dev(pgps_ctx* ctx, int B, long N, long K, int d, const double* models_host, const T* ts,
+                                const T* ys, double t0, const T* tq, T* mean, T* var, double* ll) {
+    if (!ctx || B < 1 || N < 1 || K < 1 || !models_host || !ts || !ys || !tq || !mean || !var) return PGPS_E_INVALID;
+    if (d < 1 || d > 3) return PGPS_E_UNSUPPORTED_DIM;
+    if (N + K > 0x7fffffffL) return PGPS_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t m = (size_t)(N + K);
+    T *ts_m, *ys_m;
+    int* qslot;
+    double* dll = ll;
+    TRY(stage_in<T>(ctx, ctx->st[0], nullptr, m, &ts_m));
+    TRY(stage_in<T>(ctx, ctx->st[1], nullptr, m, &ys_m));
+    TRY(stage_in<int>(ctx, ctx->st[2], nullptr, m, &qslot));
+    if (!dll) TRY(stage_in<double>(ctx, ctx->st[11], nullptr, (size_t)B, &dll));
+    TRY(launch_merge<T>(ctx, N, K, ts, ys, tq, ts_m, ys_m, qslot));        // ONE merge, shared by all models
+    return gp_predict_batch_merged<T>(ctx, B, m, K, d, models_host, ts_m, ys_m, t0, qslot, mean, var, dll);
+}
+
+template <typename T>
+static int gp_predict_batch_host(pgps_ctx* ctx, int B, long N, long K, int d, const double* models, const T* ts, const T* ys,
+                                 double t0, const T* tq, T* mean, T* var, double* ll) {
+    if (!ctx || B < 1 || N < 1 || K < 1 || !models || !ts || !ys || !tq || !mean || !var) return PGPS_E_INVALID;
+    if (d < 1 || d > 3) return PGPS_E_UNSUPPORTED_DIM;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t bk = (size_t)B * (size_t)K;
+    T *dts, *dys, *dtq, *dmean, *dvar;
+    double* dll;
+    TRY(stage_in(ctx, ctx->st[10], ts, (size_t)N, &dts));
+    TRY(stage_in(ctx, ctx->st[4], ys, (size_t)N, &dys));
+    TRY(stage_in(ctx, ctx->st[3], tq, (size_t)K, &dtq));
+    TRY(stage_in<T>(ctx, ctx->st[7], nullptr, bk, &dmean));
+    TRY(stage_in<T>(ctx, ctx->st[8], nullptr, bk, &dvar));
+    TRY(stage_in<double>(ctx, ctx->st[9], nullptr, (size_t)B, &dll));
+    TRY(gp_predict_batch_dev<T>(ctx, B, N, K, d, models, dts, dys, t0, dtq, dmean, dvar, dll));
+    std::vector<double> llh((size_t)B, 0.0);
+    const OutPart parts[3] = {{mean, dmean, bk * sizeof(T)}, {var, dvar, bk * sizeof(T)}, {llh.data(), dll, (size_t)B * sizeof(double)}};
+    TRY(copy_out(ctx, parts, 3));
+    bool finite = true;
+    for (int i = 0; i < B; ++i) {
+        if (ll) ll[i] = llh[i];
+        finite = finite && std::isfinite(llh[i]);
+    }
+    return finite ? PGPS_OK : PGPS_E_NUMERIC;
+}
+
+#define PGPS_DEFINE_PREDICT_BATCH(SUF, T)                                                                             \
+    extern "C" int pgps_gp_predict_batch_dev_##SUF(pgps_ctx* c, int B, long N, long K, int d, const double* models,   \
+                                                   const T* ts, const T* ys, double t0, const T* tq, T* mean, T* var, \
+                                                   double* ll) {                                                      \
+        return gp_predict_batch_dev<T>(c, B, N, K, d, models, ts, ys, t0, tq, mean, var, ll);                         \
+    }                                                                                                                 \
+    extern "C" int pgps_gp_predict_batch_##SUF(pgps_ctx* c, int B, long N, long K, int d, const double* models,       \
+                                               const T* ts, const T* ys, double t0, const T* tq, T* mean, T* var,     \
+                                               double* ll) {                                                          \
+        return gp_predict_batch_host<T>(c, B, N, K, d, models, ts, ys, t0, tq, mean, var, ll);                        \
+    }
+
+PGPS_DEFINE_PREDICT_BATCH(f64, double)
+PGPS_DEFINE_PREDICT_BATCH(f32, float)
+
+// Moments of the mixture sum_b w_b N(mean_b, var_b) per query column: mix = sum_b w_b mean_b, then
+// var = sum_b w_b (var_b + (mean_b - mix)^2) -- two passes over the B rows, every term of the variance non-negative.  Lane x =
+// query column (a wave reads 64 consecutive columns of a row: coalesced), the kMixRows lanes of a column take the rows
+// b = y, y + kMixRows, ... and their partial sums are added in the order y = 0, 1, ...: the same bits on every run.
+constexpr int kMixCols = 64, kMixRows = 8;
+__global__ __launch_bounds__(kMixCols * kMixRows) void k_mix_moments(int B, long K, const double* __restrict__ mean,
+                                                                     const double* __restrict__ var,
+                                                                     const double* __restrict__ w, double* __restrict__ mean_out,
+                                                                     double* __restrict__ var_out) {
+    __shared__ double part[kMixRows][kMixCols];
+    __shared__ double mix[kMixCols];
+    const int x = threadIdx.x, y = threadIdx.y;
+    const long k = (long)blockIdx.x * kMixCols + x;
+    const bool in = k < K;
+    const double equal = 1.0 / (double)B;
+    double acc = 0.0;
+    if (in)
+        for (int b = y; b < B; b += kMixRows) acc += (w ? w[b] : equal) * mean[(size_t)b * K + k];
+    part[y][x] = acc;
+    __syncthreads();
+    if (y == 0) {
+        double t = 0.0;
+#pragma unroll
+        for (int r = 0; r < kMixRows; ++r) t += part[r][x];
+        mix[x] = t;
+        if (in) mean_out[k] = t;
+    }
+    __syncthreads();
+    const double mu = mix[x];
+    acc = 0.0;
+    if (in)
+        for (int b = y; b < B; b += kMixRows) {
+            const double dlt = mean[(size_t)b * K + k] - mu;
+            acc += (w ? w[b] : equal) * (var[(size_t)b * K + k] + dlt * dlt);
+        }
+    part[y][x] = acc;
+    __syncthreads();
+    if (y == 0 && in) {
+        double t = 0.0;
+#pragma unroll
+        for (int r = 0; r < kMixRows; ++r) t += part[r][x];
+        var_out[k] = t;
+    }
+}
+
+static int mix_moments_dev(pgps_ctx* ctx, int B, long K, const double* mean, const double* var, const double* w,
+                           double* mean_out, double* var_out) {
+    if (!ctx || B < 1 || K < 1 || !mean || !var || !mean_out || !var_out) return PGPS_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const dim3 grid((unsigned)((K + kMixCols - 1) / kMixCols)), block(kMixCols, kMixRows);
+    k_mix_moments<<<grid, block, 0, ctx->stream>>>(B, K, mean, var, w, mean_out, var_out);
+    HIPCHK(ctx, hipGetLastError());
+    return PGPS_OK;
+}
+extern "C" int pgps_mix_moments_dev_f64(pgps_ctx* ctx, int B, long K, const double* mean, const double* var, const double* w,
+                                        double* mean_out, double* var_out) {
+    return mix_moments_dev(ctx, B, K, mean, var, w, mean_out, var_out);
+}
+
+// Results of a batch on a resident series.  Small unreduced results are written by the kernels straight into the series'
+// pinned host buffer, as the single predict's are (no copy-back blit: at N = 2^17, K = 2^15, B = 8 the bounce through
+// copy_out made the batch slower than eight single calls); larger ones and the mixture go through copy_out.
+constexpr size_t kBatchZeroCopyMax = (size_t)8 << 20;
+struct SeriesBatchOut {
+    double *dmean = nullptr, *dvar = nullptr, *dll = nullptr, *dmix = nullptr, *dw = nullptr;
+    bool zero = false;
+};
+static int series_batch_begin(pgps_series* s, int B, const double* w, SeriesBatchOut& o) {
+    pgps_ctx* ctx = s->ctx;
+    const size_t K = (size_t)s->K, bk = (size_t)B * K;
+    if (!w && s->zero_copy && (2 * bk + (size_t)B) * sizeof(double) <= kBatchZeroCopyMax) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));         // (the buffer may be replaced: nothing may still write it)
+        if (series_host(s, 2 * bk + (size_t)B + 64) == PGPS_OK && s->zero_copy) {
+            o.zero = true;
+            o.dmean = s->hdev; o.dvar = s->hdev + bk; o.dll = s->hdev + 2 * bk;
+            return PGPS_OK;
+        }
+        // the pinned buffer could not be had at this size: the staged path below needs none of it.  The series keeps a
+        // buffer for its single calls (2 K + 64 doubles), or says so
+        if (!s->host && series_host(s, 2 * (size_t)s->K + 64) != PGPS_OK) return PGPS_E_NOMEM;
+    }
+    TRY(stage_in<double>(ctx, ctx->st[7], nullptr, bk, &o.dmean));
+    TRY(stage_in<double>(ctx, ctx->st[8], nullptr, bk, &o.dvar));
+    TRY(stage_in<double>(ctx, ctx->st[9], nullptr, (size_t)B, &o.dll));
+    if (w) {
+        TRY(stage_in<double>(ctx, ctx->st[3], nullptr, 2 * K, &o.dmix));
+        TRY(stage_in<double>(ctx, ctx->st[4], w, (size_t)B, &o.dw));
+    }
+    return PGPS_OK;
+}
+static int series_batch_end(pgps_series* s, int B, const double* w, const SeriesBatchOut& o, double* mean, double* var,
+                            double* ll) {
+    pgps_ctx* ctx = s->ctx;
+    const size_t K = (size_t)s->K, bk = (size_t)B * K;
+    std::vector<double> llh((size_t)B, 0.0);
+    if (o.zero) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        std::memcpy(mean, s->host, bk * sizeof(double));
+        std::memcpy(var, s->host + bk, bk * sizeof(double));
+        std::memcpy(llh.data(), s->host + 2 * bk, (size_t)B * sizeof(double));
+    } else {
+        if (w) TRY(mix_moments_dev(ctx, B, s->K, o.dmean, o.dvar, o.dw, o.dmix, o.dmix + K));
+        const size_t nout = (w ? K : bk) * sizeof(double);
+        const OutPart parts[3] = {{mean, w ? o.dmix : o.dmean, nout}, {var, w ? o.dmix + K : o.dvar, nout},
+                                  {llh.data(), o.dll, (size_t)B * sizeof(double)}};
+        TRY(copy_out(ctx, parts, 3));
+    }
+    bool finite = true;
+    for (int i = 0; i < B; ++i) {
+        if (ll) ll[i] = llh[i];
+        finite = finite && std::isfinite(llh[i]);
+    }
+    return finite ? PGPS_OK : PGPS_E_NUMERIC;
+}
+
+// the batch on the resident series and its merged query grid.  w == NULL: mean, var (B, K) on the host; else w = B mixture
+// weights (host, used as given) and mean, var (K): the (B, K) results stay on the device, k_mix_moments reduces them there
+extern "C" int pgps_series_gp_predict_batch_f64(pgps_series* s, int B, int d, const double* models, const double* w,
+                                                double* mean, double* var, double* ll) {
+    if (!s || B < 1 || s->K < 1 || !models || !mean || !var) return PGPS_E_INVALID;
+    if (d < 1 || d > 3) return PGPS_E_UNSUPPORTED_DIM;
+    pgps_ctx* ctx = s->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    SeriesBatchOut o;
+    TRY(series_batch_begin(s, B, w, o));
+    TRY(gp_predict_batch_merged<double>(ctx, B, (size_t)(s->N + s->K), s->K, d, models, s->ts_m, s->ys_m, s->t0, s->qslot, o.dmean,
+                                        o.dvar, o.dll));
+    return series_batch_end(s, B, w, o, mean, var, ll);
+}
+
+// ---------------------------------------------------------------------------------------------
+// batched predict_f for ANY kernel's LTI model (fp64, 2 <= d <= 16): B models [F | Pinf | H | R] over one series and one
+// query grid.  ONE merge, one batched discretisation, then the row-cooperative filter + smoother + projection of all
+// models of a group side by side (blockIdx.y = model: model_view, pgps_rc.hip.h) -- the launches of ONE predict, whatever B.
+// ---------------------------------------------------------------------------------------------
+// default budget of the general-LTI batch (a model is ~3 (N + K) d^2 doubles, 12.6 MB at d = 11, N + K = 4216): d = 11, B = 64
+// measured 34.7, 23.4, 16.6, 13.6, 12.6 ms at 8, 32, 64, 256 MiB and 1 GiB -- still improving at the largest budget measured,
+// where the whole batch is one group
+constexpr size_t kBatchScratchDefaultLti = (size_t)1 << 30;
+static int lti_predict_batch_merged(pgps_ctx* ctx, int B, size_t m, long K, int d, const double* models, const double* ts_m,
+                                    const double* ys_m, double t0, const int* qslot, double* mean, double* var, double* ll) {
+    const size_t dd = (size_t)d * d, ms = 2 * dd + d + 1;
+    for (int b = 0; b < B; ++b)
+        if (!(models[(size_t)b * ms + ms - 1] > 0.0)) return PGPS_E_INVALID;
+    // per model: Fs, the stored smoothing elements E (as much again) and g, plus L and the chain records inside the scan's
+    // own workspace -- about 3 m d^2 doubles; the models run in groups that fit the context's batch budget
+    const size_t per_model = (3 * m * dd + m * d) * sizeof(double);
+    const size_t budget = ctx->batch_scratch ? ctx->batch_scratch : kBatchScratchDefaultLti;
+    size_t group = budget / per_model;
+    if (group < 1) group = 1;
+    if (group > (size_t)B) group = (size_t)B;
+    if (group > 65535) group = 65535;                   // grid.y
+    double *table, *Fs, *Es, *gs;
+    TRY(stage_in<double>(ctx, ctx->lti[0], models, (size_t)B * ms, &table));
+    TRY(stage_in<double>(ctx, ctx->lti[4], nullptr, group * m * dd, &Fs));
+    TRY(stage_in<double>(ctx, ctx->lti[6], nullptr, group * m * dd, &Es));
+    TRY(stage_in<double>(ctx, ctx->lti[7], nullptr, group * m * d, &gs));
+    for (size_t g0 = 0; g0 < (size_t)B; g0 += group) {
+        const int G = (int)((size_t)B - g0 < group ? (size_t)B - g0 : group);
+        const double* tab = table + g0 * ms;
+        TRY(launch_disc_rc(ctx, (long)m, d, tab, tab + dd, ts_m, t0, Fs, nullptr, G, (long)ms));     // implicit process noise
+        TRY(launch_predict_batch_rc(ctx, (long)m, K, d, G, B, tab, (long)ms, Fs, ys_m, qslot, Es, gs, mean + g0 * (size_t)K,
+                                    var + g0 * (size_t)K, ll + g0));
+    }
+    return PGPS_OK;
+}
+
+static int lti_predict_batch_dev(pgps_ctx* ctx, int B, long N, long K, int d, const double* models, const double* ts,
+                                 const double* ys, double t0, const double* tq, double* mean, double* var, double* ll) {
+    if (!ctx || B < 1 || N < 1 || K < 1 || !models || !ts || !ys || !tq || !mean || !var) return PGPS_E_INVALID;
+    if (d < rc::kDimMin || d > rc::kDimMax) return PGPS_E_UNSUPPORTED_DIM;
+    if (N + K > 0x7fffffffL) return PGPS_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t m = (size_t)(N + K);
+    double *tsm, *ysm, *dll = ll;
+    int* qslot;
+    TRY(stage_in<double>(ctx, ctx->lti[1], nullptr, m, &tsm));
+    TRY(stage_in<double>(ctx, ctx->lti[2], nullptr, m, &ysm));
+    TRY(stage_in<int>(ctx, ctx->lti[3], nullptr, m, &qslot));
+    if (!dll) TRY(stage_in<double>(ctx, ctx->st[6], nullptr, (size_t)B, &dll));
+    TRY(launch_merge<double>(ctx, N, K, ts, ys, tq, tsm, ysm, qslot));
+    return lti_predict_batch_merged(ctx, B, m, K, d, models, tsm, ysm, t0, qslot, mean, var, dll);
+}
+
+extern "C" int pgps_lti_predict_batch_dev_f64(pgps_ctx* c, int B, long N, long K, int d, const double* models, const double* ts,
+                                              const double* ys, double t0, const double* tq, double* mean, double* var,
+                                              double* ll) {
+    return lti_predict_batch_dev(c, B, N, K, d, models, ts, ys, t0, tq, mean, var, ll);
+}
+
+extern "C" int pgps_lti_predict_batch_f64(pgps_ctx* ctx, int B, long N, long K, int d, const double* models, const double* ts,
+                                          const double* ys, double t0, const double* tq, double* mean, double* var, double* ll) {
+    if (!ctx || B < 1 || N < 1 || K < 1 || !models || !ts || !ys || !tq || !mean || !var) return PGPS_E_INVALID;
+    if (d < rc::kDimMin || d > rc::kDimMax) return PGPS_E_UNSUPPORTED_DIM;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t bk = (size_t)B * (size_t)K;
+    double *dts, *dys, *dtq, *dmean, *dvar, *dll;
+    TRY(stage_in(ctx, ctx->st[10], ts, (size_t)N, &dts));
+    TRY(stage_in(ctx, ctx->st[4], ys, (size_t)N, &dys));
+    TRY(stage_in(ctx, ctx->st[3], tq, (size_t)K, &dtq));
+    TRY(stage_in<double>(ctx, ctx->st[7], nullptr, bk, &dmean));
+    TRY(stage_in<double>(ctx, ctx->st[8], nullptr, bk, &dvar));
+    TRY(stage_in<double>(ctx, ctx->st[9], nullptr, (size_t)B, &dll));
+    TRY(lti_predict_batch_dev(ctx, B, N, K, d, models, dts, dys, t0, dtq, dmean, dvar, dll));
+    std::vector<double> llh((size_t)B, 0.0);
+    const OutPart parts[3] = {{mean, dmean, bk * 8}, {var, dvar, bk * 8}, {llh.data(), dll, (size_t)B * 8}};
+    TRY(copy_out(ctx, parts, 3));
+    bool finite = true;
+    for (int i = 0; i < B; ++i) {
+        if (ll) ll[i] = llh[i];
+        finite = finite && std::isfinite(llh[i]);
+    }
+    return finite ? PGPS_OK : PGPS_E_NUMERIC;
+}
+
+extern "C" int pgps_series_lti_predict_batch_f64(pgps_series* s, int B, int d, const double* models, const double* w,
+                                                 double* mean, double* var, double* ll) {
+    if (!s || B < 1 || s->K < 1 || !models || !mean || !var) return PGPS_E_INVALID;
+    if (d < rc::kDimMin || d > rc::kDimMax) return PGPS_E_UNSUPPORTED_DIM;
+    pgps_ctx* ctx = s->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    SeriesBatchOut o;
+    TRY(series_batch_begin(s, B, w, o));
+    TRY(lti_predict_batch_merged(ctx, B, (size_t)(s->N + s->K), s->K, d, models, s->ts_m, s->ys_m, s->t0, s->qslot, o.dmean, o.dvar,
+                                 o.dll));
+    return series_batch_end(s, B, w, o, mean, var, ll);
+}
 
 // ---------------------------------------------------------------------------------------------
 // log-likelihood and its gradient (fused path, forward-mode duals through the scan)

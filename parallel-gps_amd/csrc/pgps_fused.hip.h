@@ -242,7 +242,7 @@ __global__ __launch_bounds__(kBlock) void k_gp_apply(const GpArgs<T> g) {
 // 1e3..1e5, where one series alone cannot fill the chip).  blockIdx.y selects the model; each model
 // has its own slice of the scan scratch.  Same bodies, same arithmetic as the single-model launches.
 // ---------------------------------------------------------------------------------------------
-template <typename T, int D>
+template <typename T, int D, bool PREDICT = false>
 __device__ __forceinline__ GpArgs<T> gp_batch_select(const GpBatchArgs<T>& b) {
     const long m = blockIdx.y;
     const double* p = b.models + m * kGpModelStride;
@@ -261,6 +261,19 @@ __device__ __forceinline__ GpArgs<T> gp_batch_select(const GpBatchArgs<T>& b) {
     for (int i = 0; i < D; ++i) g.m.H[i] = T(p[28 + i]);
     g.m.ts = b.ts;
     g.m.t_prev = b.t_prev;
+    if constexpr (PREDICT) {
+        // predict (pgps_gp_predict_batch_*): the model's slices of the filtered moments and of the smoother's scan records,
+        // its output rows and its log-likelihood; the merged series and its query slots are shared.  A compile-time flavour: the
+        // log-likelihood kernels keep fms == nullptr a constant, so their store path is compiled out as it always was
+        g.s.fms = b.fms + m * b.bs_fm;
+        g.s.fPs = b.fPs + m * b.bs_fP;
+        g.s.sspine = b.sspine + m * b.nblocks * Dim<D>::NSMTH;
+        g.s.lsuf = b.lsuf + m * b.nlanes * Dim<D>::NSMTH;
+        g.s.ll = b.ll + m;
+        g.qslot = b.qslot;
+        g.pmean = b.pmean + m * b.K;
+        g.pvar = b.pvar + m * b.K;
+    }
     return g;
 }
 
@@ -271,11 +284,11 @@ __global__ __launch_bounds__(kBlock) void k_gpb_reduce(const GpBatchArgs<T> b) {
     gp_reduce_body<T, D>(g, lds);
 }
 
-template <typename T, int D>
+template <typename T, int D, bool SMOOTH = false>
 __global__ __launch_bounds__(kBlock) void k_gpb_apply(const GpBatchArgs<T> b) {
-    const GpArgs<T> g = gp_batch_select<T, D>(b);
+    const GpArgs<T> g = gp_batch_select<T, D, SMOOTH>(b);
     __shared__ GpLds<T, D> sh;
-    gp_apply_body<T, D, false, false>(g, sh);
+    gp_apply_body<T, D, SMOOTH, false>(g, sh);
 }
 
 // one workgroup per model: ll[m] = sum of its block partials
@@ -447,6 +460,36 @@ __global__ __launch_bounds__(kBlock) void k_gp_one(const GpArgs<T> g) {
     } else {
         if (threadIdx.x == 0 && g.s.ll != nullptr) *g.s.ll = g.s.llpart[0];      // (this lane wrote the partial)
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// batched predict_f (pgps_gp_predict_batch_*): B models over one merged series.  Two forms, the same three bodies:
+//   k_gpb_reduce, k_gpb_apply<.., true>, k_gpb_smooth   three launches of (nblocks, B) workgroups;
+//   k_gpb_one                                           ONE workgroup per model (grid (1, B): blockIdx.x stays the
+//                                                       workgroup's index inside its series), the three bodies back to
+//                                                       back as k_gp_one<.., 2> runs them: no spine, no second launch, and
+//                                                       with B >= the number of CUs no CU idles as it does for a single model.
+// Every model has its own slices of the scratch (gp_batch_select), so workgroups of different models share nothing but the
+// read-only series.
+// ---------------------------------------------------------------------------------------------
+template <typename T, int D>
+__global__ __launch_bounds__(kBlock) void k_gpb_smooth(const GpBatchArgs<T> b) {
+    const GpArgs<T> g = gp_batch_select<T, D, true>(b);
+    __shared__ GpLds<T, D> sh;
+    gp_smooth_body<T, D, false, true>(g, sh);
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(kBlock) void k_gpb_one(const GpBatchArgs<T> b) {
+    const GpArgs<T> g = gp_batch_select<T, D, true>(b);
+    __shared__ GpLds<T, D> sh;
+    gp_reduce_body<T, D>(g, sh.lds);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    gp_apply_body<T, D, true, false>(g, sh);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    gp_smooth_body<T, D, false, true>(g, sh);
 }
 
 }  // namespace pgps

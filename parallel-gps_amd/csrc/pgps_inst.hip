@@ -359,6 +359,91 @@ int launch_gp_batch(pgps_ctx* ctx, int B, GpBatchArgs<T> b) {
     }
 }
 
+// ---- batched predict_f (B models over one merged series of b.N steps) ------------------------------------
+template <typename T, int D>
+int launch_gp_predict_batch(pgps_ctx* ctx, int B, GpBatchArgs<T> b) {
+    if constexpr (D <= 3) {
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        // form and geometry are fixed HERE, once per call, from (B, N): a model's result then depends neither on the group
+        // it runs in nor on the other models
+        // automatic = form 2: measured equal to form 1 within the spread up to B = 512 and faster at B = 1000.
+        // Form 1 is honoured up to kBatchOneMax merged steps (one workgroup walks the whole series: 256 steps per lane there)
+        const bool one = ctx->batch_form == 1 && b.N <= kBatchOneMax;
+        int lc;
+        if (one) {
+            long v = (b.N + kBlock - 1) / kBlock;
+            v = (v + 3) / 4 * 4;
+            if (v > 0x7fffffffL) return PGPS_E_INVALID;
+            lc = (int)v;
+        } else {
+            // as launch_gp_batch: 16 steps per lane while the batch keeps the chip covered, halved towards 4 when B x N is small
+            lc = ctx->chunk;
+            if (lc <= 0) {
+                lc = 16;
+                while (lc > 4 && (long)B * ((b.N + (long)kBlock * lc - 1) / ((long)kBlock * lc)) < 1024) lc /= 2;
+                if (b.N < (long)kBlock * 4) lc = (int)((b.N + kBlock - 1) / kBlock);
+                if (lc < 1) lc = 1;
+            }
+        }
+        b.Lc = lc;
+        b.nblocks = one ? 1 : (int)((b.N + (long)kBlock * lc - 1) / ((long)kBlock * lc));
+        b.nlanes = (long)b.nblocks * kBlock;
+        if (b.nblocks > 65535) return PGPS_E_INVALID;    // (6.7e7 merged steps at 4 per lane: one model's scratch would be 10 GB)
+        // scratch of ONE model, every part a multiple of 256 bytes
+        const size_t nb = (size_t)b.nblocks, nl = (size_t)b.nlanes, n = (size_t)b.N;
+        auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+        const size_t s_spine = up(nb * Dim<D>::NFILT * sizeof(T)), s_lpre = up(nl * Dim<D>::NFILT * sizeof(T));
+        const size_t s_sspine = up(nb * Dim<D>::NSMTH * sizeof(T)), s_lsuf = up(nl * Dim<D>::NSMTH * sizeof(T));
+        const size_t s_ll = up(nb * sizeof(double)), s_fm = up(n * D * sizeof(T)), s_fP = up(n * D * D * sizeof(T));
+        const size_t per_model = s_spine + s_lpre + s_sspine + s_lsuf + s_ll + s_fm + s_fP;
+        const size_t budget = ctx->batch_scratch ? ctx->batch_scratch : kBatchScratchDefault;
+        size_t group = budget / per_model;
+        if (group < 1) group = 1;                       // (one model is the least a launch can hold)
+        if (group > (size_t)B) group = (size_t)B;
+        if (group > 65535) group = 65535;               // grid.y
+        int rc = ensure(ctx, ctx->ws, group * per_model);
+        if (rc) return rc;
+        // the slices of a kind lie side by side (gp_batch_select strides them by the UNROUNDED record counts for the scan
+        // records, as launch_gp_batch does, and by bs_fm / bs_fP for the moments)
+        char* base = (char*)ctx->ws.p;
+        size_t off = 0;
+        b.spine = (T*)(base + off);  off += up(group * nb * Dim<D>::NFILT * sizeof(T));
+        b.lpre = (T*)(base + off);   off += up(group * nl * Dim<D>::NFILT * sizeof(T));
+        b.sspine = (T*)(base + off); off += up(group * nb * Dim<D>::NSMTH * sizeof(T));
+        b.lsuf = (T*)(base + off);   off += up(group * nl * Dim<D>::NSMTH * sizeof(T));
+        b.llpart = (double*)(base + off); off += up(group * nb * sizeof(double));
+        b.fms = (T*)(base + off);    off += group * s_fm;
+        b.fPs = (T*)(base + off);    off += group * s_fP;
+        b.bs_fm = (long)(s_fm / sizeof(T));
+        b.bs_fP = (long)(s_fP / sizeof(T));
+        const double* models = b.models;
+        T* pmean = b.pmean;
+        T* pvar = b.pvar;
+        double* ll = b.ll;
+        const dim3 block(kBlock);
+        for (size_t g0 = 0; g0 < (size_t)B; g0 += group) {
+            const unsigned G = (unsigned)((size_t)B - g0 < group ? (size_t)B - g0 : group);
+            b.models = models + g0 * kGpModelStride;
+            b.pmean = pmean + g0 * (size_t)b.K;
+            b.pvar = pvar + g0 * (size_t)b.K;
+            b.ll = ll + g0;
+            if (one) {
+                timed_launch(ctx, PGPS_K_FILTER_APPLY, k_gpb_one<T, D>, dim3(1, G), block, 0, b);
+            } else {
+                const dim3 grid(b.nblocks, G);
+                timed_launch(ctx, PGPS_K_FILTER_REDUCE, k_gpb_reduce<T, D>, grid, block, 0, b);
+                timed_launch(ctx, PGPS_K_FILTER_APPLY, k_gpb_apply<T, D, true>, grid, block, 0, b);
+                timed_launch(ctx, PGPS_K_SMOOTHER_APPLY, k_gpb_smooth<T, D>, grid, block, 0, b);
+            }
+            HIPCHK(ctx, hipGetLastError());
+        }
+        return PGPS_OK;
+    } else {
+        (void)ctx; (void)B; (void)b;
+        return PGPS_E_UNSUPPORTED_DIM;
+    }
+}
+
 // ---- fused path: log-likelihood and the model's adjoints (pgps_gpadj.hip.h), fp64 units of d <= 3 ---------------------
 template <typename T, int D>
 int launch_gp_adj(pgps_ctx* ctx, GpArgs<double> g, double* out) {
@@ -408,6 +493,7 @@ int launch_gp_adj(pgps_ctx* ctx, GpArgs<double> g, double* out) {
 template int launch_gp_adj<PGPS_INST_T, PGPS_INST_D>(pgps_ctx*, GpArgs<double>, double*);
 
 template int launch_gp_batch<PGPS_INST_T, PGPS_INST_D>(pgps_ctx*, int, GpBatchArgs<PGPS_INST_T>);
+template int launch_gp_predict_batch<PGPS_INST_T, PGPS_INST_D>(pgps_ctx*, int, GpBatchArgs<PGPS_INST_T>);
 template int launch_gp<PGPS_INST_T, PGPS_INST_D>(pgps_ctx*, GpArgs<PGPS_INST_T>, int, int);
 template int launch_scan<PGPS_INST_T, PGPS_INST_D>(pgps_ctx*, ScanArgs<PGPS_INST_T>, Mode);
 template int launch_disc<PGPS_INST_T, PGPS_INST_D>(pgps_ctx*, long, const PGPS_INST_T*, const PGPS_INST_T*,

@@ -26,6 +26,8 @@ struct pgps_ctx {
     int single_pass = -1;               // single-pass filter kernel: -1 = auto, 0 = off, 1 = on
     int lookback_window = 256;          // tiles per look-back window (<= 256; small values are for tests)
     int block = 0;                      // lane-chunk workgroups: 0 = auto, 128 / 256 lanes (pgps_set_block)
+    size_t batch_scratch = 0;           // batched predict: scratch budget in bytes, 0 = kBatchScratchDefault (pgps_set_batch_scratch)
+    int batch_form = 0;                 // batched fused predict: 0 = automatic, 1 = one workgroup per model, 2 = three launches (pgps_set_batch_form)
     int one_launch = -1;                // fused (pgps_gp_*) calls of short series in ONE launch: -1 = auto (N <= kOneLaunchAuto), 0 = never, n > 0 = up to n steps
     long grad_pack = -1;                // gradient at d <= 2: one direction per model up to this many steps (-1 = automatic, 0 = never)
     int rc_scan = -1;                   // scans of the chain totals (row- / quad-cooperative families): -1 = auto, 0 = one launch per Kogge-Stone level, 1 = blocked (pgps_set_rc_scan)
@@ -57,6 +59,8 @@ struct pgps_ctx {
     // small host-array calls (pgps_gp_predict_*, pgps_lti_predict_f64, ...): one pinned arena, ONE copy in and ONE copy out
     char* pin_h = nullptr;              // hipHostMalloc, kPinArena bytes, made at the first small call
     DevBuf pin_d;                       // its device twin
+    char* out_h = nullptr;              // pinned staging of the batched predict's (B, K) results on their way to pageable host arrays
+    size_t out_cap = 0;
     DevBuf gadj;                        // fused-path adjoint gradient (pgps_gpadj.hip.h): kept states of the forward pass, workgroup partials
     DevBuf wide[9];                     // fp64 copies of a promoted float32 call's arrays: P0, H, Fs, Qs, ys, fms, fPs, sms, sPs
     DevBuf smp;                         // backward sampler (pgps_sample.hip.h): lane suffixes and spine of every sample group
@@ -262,11 +266,32 @@ struct GpBatchArgs {
     T* lpre;                    // (B, NFILT, nlanes)
     double* llpart;             // (B, nblocks)
     double* ll;                 // (B,)
+    // predict (pgps_gp_predict_batch_*; all null / 0 in the log-likelihood call): N counts the merged steps
+    T* fms;                     // (B, bs_fm) filtered means of the merged steps, one slice per model
+    T* fPs;                     // (B, bs_fP) filtered covariances
+    long bs_fm, bs_fP;          // slice strides in elements (>= N d, N d^2; rounded so that every slice starts 256-byte aligned)
+    T* sspine;                  // (B, nblocks, NSMTH)
+    T* lsuf;                    // (B, NSMTH, nlanes)
+    const int* qslot;           // (N,) slot of a query step in a model's output row, -1 at the training steps (shared)
+    T* pmean;                   // (B, K)
+    T* pvar;                    // (B, K)
+    long K;
 };
 constexpr int kGpModelStride = 32;
 
 template <typename T, int D>
 int launch_gp_batch(pgps_ctx* ctx, int B, GpBatchArgs<T> b);
+// predict_f of B models over one merged series (b.N merged steps, b.qslot, b.K, b.models, b.pmean, b.pvar, b.ll set by the
+// caller): picks the form and the geometry once from (B, N), carves the scratch and runs the models in groups that fit the
+// context's batch budget
+template <typename T, int D>
+int launch_gp_predict_batch(pgps_ctx* ctx, int B, GpBatchArgs<T> b);
+// scratch budget of the batched fused predict when pgps_set_batch_scratch has not set one: the smallest budget beyond which
+// the measured time per model no longer improves (B = 1000, N + K = 5000, d = 2: 3.79, 2.83, 2.35, 2.19 ms at 8, 16, 32, 64 MiB,
+// 2.2 .. 2.7 ms at 256 MiB and 1 GiB)
+constexpr size_t kBatchScratchDefault = 64u << 20;
+// form 1 of the batched fused predict (one workgroup per model, pgps_set_batch_form(ctx, 1)) is taken up to this many merged steps
+constexpr long kBatchOneMax = 65536;
 
 // merge of two sorted time arrays on the device + NaN marking of the query rows (pgps_core.hip)
 template <typename T>
@@ -375,6 +400,13 @@ int launch_disc_rc(pgps_ctx* ctx, long N, int d, const double* F, const double* 
 // Fs / Qs = (batch, N, d, d) discretised arrays, ll = (batch,) device
 int launch_ll_batch_rc(pgps_ctx* ctx, long N, int d, int batch, const double* table, long bs_model, const double* Fs,
                        const double* Qs, const double* ys, double* ll);
+// predict_f of `batch` models over one MERGED series of N steps (qslot marks the K query rows): table / Fs as above, Es / gs
+// = (batch, N, d, d) / (batch, N, d) scratch for the smoothing elements, pmean / pvar (batch, K), ll (batch,), all device.
+// geom_batch (>= batch) = the models of the whole call: the chain length is fixed from it, so a group's results do not
+// depend on how the call was split
+int launch_predict_batch_rc(pgps_ctx* ctx, long N, long K, int d, int batch, int geom_batch, const double* table, long bs_model,
+                            const double* Fs, const double* ys, const int* qslot, double* Es, double* gs, double* pmean,
+                            double* pvar, double* ll);
 namespace rc {
 constexpr int kDimMin = 2, kDimMax = 16;
 constexpr int kScanBlockedDimMax = 15;     // blocked scans of the chain totals: the dimensions whose kernels need no scratch
@@ -402,6 +434,7 @@ struct RcArgsT {
     const Real* carry_back;   // !seg_last: compact smoother record of everything after the segment
     int batch;                  // models evaluated over the same series (blockIdx.y); 0 / 1 = one
     long bs_F, bs_agg, bs_model;    // per-model strides of Fs / Qs, of agg1 / pre, of the model table
+    long bs_sagg, bs_g, bs_out;     // batched predict (0 otherwise): per-model strides of sagg1 / suf, of gs (Es / Lws: bs_F), of pmean / pvar
     const Real* Rs;           // batch entry point: observation noise of model b at Rs[b * bs_model] (else null)
     int implicit_q;             // Qs is not there: Q_k = P0 - F_k P0 F_k^T is folded into the predict (P0 stationary)
     int store_f;                // write fms / fPs (0: log-likelihood-only and projected-posterior calls)

@@ -608,7 +608,7 @@ struct Io {
     }
 };
 
-// Batched evaluation (pgps_lti_ll_batch_*): blockIdx.y selects one of `batch` models over the same series; each
+// Batched evaluation (pgps_lti_ll_batch_*, pgps_lti_predict_batch_*): blockIdx.y selects one of `batch` models over the same series; each
 // model has its own slice of the discretised arrays, of the scan scratch and of the model table
 // [F | Pinf | H | R] (stride bs_model).  The kernel bodies below never see the difference.
 template <typename Real>
@@ -623,6 +623,13 @@ __device__ __forceinline__ RcArgsT<Real> model_view(const RcArgsT<Real>& a) {
         b.agg1 += mb * a.bs_agg;
         b.pre += mb * a.bs_agg;
         b.llpart += mb * a.nchunk;
+        if (a.bs_out) {         // batched predict: the model's smoothing totals, stored elements and output rows
+            b.sagg1 += mb * a.bs_sagg;
+            b.suf += mb * a.bs_sagg;
+            b.Es += mb * a.bs_F; b.Lws += mb * a.bs_F;
+            b.gs += mb * a.bs_g;
+            b.pmean += mb * a.bs_out; b.pvar += mb * a.bs_out;
+        }
     }
     return b;
 }
@@ -1327,7 +1334,8 @@ __device__ __forceinline__ void smooth1_body(const RcArgsT<Real>& a, Real* patch
 }
 
 template <typename Real, int D, bool PROJ>
-__global__ __launch_bounds__(64) void rc_smooth1(const RcArgsT<Real> a) {
+__global__ __launch_bounds__(64) void rc_smooth1(const RcArgsT<Real> a0) {
+    const RcArgsT<Real> a = model_view(a0);
     __shared__ Real tl[4 * kPatch];
     const int lane = threadIdx.x & 15, row = threadIdx.x >> 4;
     __shared__ __attribute__((aligned(16))) char wslots[3 * (Io<D, Real>::SLOT + 16)];
@@ -1506,10 +1514,12 @@ __global__ __launch_bounds__(64) void rc_ks_filter(long n, long stride, const Re
 // (fixblk > 0: record c takes fixed[c / fixblk + 1], the scanned total of the blocks after its own; the last block passes)
 template <typename Real, int D>
 __global__ __launch_bounds__(64) void rc_ks_smoother(long n, long stride, const Real* in, Real* out, const Real* fixed,
-                                                     long fixblk = 0) {
+                                                     long fixblk = 0, long bstride = 0) {
     __shared__ Real tl[4 * kPatch];
     const int lane = threadIdx.x & 15, row = threadIdx.x >> 4;
     Real* patch = patch_init(tl, row);
+    in += blockIdx.y * bstride;         // batched: one model per blockIdx.y
+    out += blockIdx.y * bstride;
     constexpr int dd = D * D, ns = 2 * D * D + D;
     const long c = (long)blockIdx.x * 4 + row;
     const long nblk = fixblk > 0 ? (n + fixblk - 1) / fixblk : 0;
@@ -1892,7 +1902,7 @@ int launch_rc_ks(pgps_ctx* ctx, int which, long n, long stride, const Real* in, 
                  const Real* fixed) {
     const dim3 blk(64), g((unsigned)((n + 3) / 4), (unsigned)batch);
     if (which == 0) timed_launch(ctx, PGPS_K_FILTER_REDUCE, rc_ks_filter<Real, D>, g, blk, 0u, n, stride, in, out, bstride, fixed, 0L);
-    else timed_launch(ctx, PGPS_K_SMOOTHER_REDUCE, rc_ks_smoother<Real, D>, g, blk, 0u, n, stride, in, out, fixed, 0L);
+    else timed_launch(ctx, PGPS_K_SMOOTHER_REDUCE, rc_ks_smoother<Real, D>, g, blk, 0u, n, stride, in, out, fixed, 0L, bstride);
     HIPCHK(ctx, hipGetLastError());
     return PGPS_OK;
 }
@@ -1941,7 +1951,7 @@ int launch_rc_scan_blocked(pgps_ctx* ctx, int which, long n, Real* data, Real* s
         if (rcode) return rcode;
         const dim3 g((unsigned)((n + 3) / 4));
         if (which == 0) timed_launch(ctx, PGPS_K_FILTER_REDUCE, rc_ks_filter<Real, D>, g, dim3(64), 0u, n, 0L, (const Real*)data, data, 0L, (const Real*)scratch, (long)B);
-        else timed_launch(ctx, PGPS_K_SMOOTHER_REDUCE, rc_ks_smoother<Real, D>, g, dim3(64), 0u, n, 0L, (const Real*)data, data, (const Real*)scratch, (long)B);
+        else timed_launch(ctx, PGPS_K_SMOOTHER_REDUCE, rc_ks_smoother<Real, D>, g, dim3(64), 0u, n, 0L, (const Real*)data, data, (const Real*)scratch, (long)B, 0L);
         HIPCHK(ctx, hipGetLastError());
     }
     return PGPS_OK;

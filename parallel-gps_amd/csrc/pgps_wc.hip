@@ -2287,8 +2287,10 @@ static inline bool scan_is_blocked(const pgps_ctx* ctx, long n, int batch, int d
 }
 // inclusive scan of the n records in A (B: second buffer / scratch); *res = where the result is
 template <typename Real>
-static int ks_scan(pgps_ctx* ctx, int d, int which, long n, Real* A, Real* B, Real** res, int batch = 1, long bstride = 0) {
-    if (scan_is_blocked(ctx, n, batch, d)) {
+static int ks_scan(pgps_ctx* ctx, int d, int which, long n, Real* A, Real* B, Real** res, int batch = 1, long bstride = 0,
+                   int geom_batch = 0) {
+    // (a group of a larger batched call scans as the whole call does, also a group of one: results must not depend on the split)
+    if (scan_is_blocked(ctx, n, geom_batch > batch ? geom_batch : batch, d)) {
         *res = A;
         return scan_blocked(ctx, d, which, n, A, B);
     }
@@ -2395,7 +2397,7 @@ static int scan_rc_seg(pgps_ctx* ctx, int d, RcArgsT<Real> a, Mode mode, Real* a
 
 template <typename Real>
 static int scan_rc(pgps_ctx* ctx, int d, RcArgsT<Real> a, Mode mode, Real* aggA, Real* aggB, Real* saggA, Real* saggB,
-                   double* ll) {
+                   double* ll, int geom_batch = 0) {
     int rcode;
     if (mode == MODE_PKS) {                     // stand-alone smoother: elements from the given filtered moments
         a.sagg1 = saggA;
@@ -2409,13 +2411,13 @@ static int scan_rc(pgps_ctx* ctx, int d, RcArgsT<Real> a, Mode mode, Real* aggA,
     if ((rcode = level1(ctx, d, a, 0))) return rcode;
     Real* src = aggA;
     const int nb = a.batch > 1 ? a.batch : 1;
-    if ((rcode = ks_scan(ctx, d, 0, a.nchunk, aggA, aggB, &src, nb, a.bs_agg))) return rcode;
+    if ((rcode = ks_scan(ctx, d, 0, a.nchunk, aggA, aggB, &src, nb, a.bs_agg, geom_batch))) return rcode;
     a.pre = src;
     if (mode == MODE_PKFS) {
         a.sagg1 = saggA;
         if ((rcode = level1(ctx, d, a, 1))) return rcode;
         src = saggA;
-        if ((rcode = ks_scan(ctx, d, 1, a.nchunk, saggA, saggB, &src))) return rcode;
+        if ((rcode = ks_scan(ctx, d, 1, a.nchunk, saggA, saggB, &src, nb, a.bs_sagg, geom_batch))) return rcode;
         a.suf = src;
         if ((rcode = level1(ctx, d, a, a.qslot ? 4 : 3))) return rcode;
     } else {
@@ -2448,7 +2450,7 @@ static inline size_t rc_align(size_t x) { return (x + 255) / 256 * 256; }
 
 template <typename Real>
 static int scan_rc_entry(pgps_ctx* ctx, ScanArgs<Real> sa, int d, Mode mode, int store_f, const int* qslot, Real* pmean,
-                         Real* pvar, int batch = 1, long bs_model = 0);
+                         Real* pvar, int batch = 1, long bs_model = 0, int geom_batch = 0, long bs_out = 0);
 
 // 2 <= d <= 16, pkf / pks / pkfs on one device and the three segment phases
 template <typename Real>
@@ -2477,9 +2479,25 @@ int launch_ll_batch_rc(pgps_ctx* ctx, long N, int d, int batch, const double* ta
     return scan_rc_entry<double>(ctx, a, d, MODE_PKF, 0, nullptr, nullptr, nullptr, batch, bs_model);
 }
 
+int launch_predict_batch_rc(pgps_ctx* ctx, long N, long K, int d, int batch, int geom_batch, const double* table, long bs_model,
+                            const double* Fs, const double* ys, const int* qslot, double* Es, double* gs, double* pmean,
+                            double* pvar, double* ll) {
+    RoctxRange range_("parallel_filter");
+    if (batch < 1 || geom_batch < batch || K < 1 || !table || !Fs || !ys || !qslot || !Es || !gs || !pmean || !pvar || !ll)
+        return PGPS_E_INVALID;
+    const long dd = (long)d * d;
+    ScanArgs<double> a{};
+    a.N = N; a.seg_first = 1; a.seg_last = 1;
+    a.P0 = table + dd; a.H = table + 2 * dd; a.R = 0.0; a.Fs = Fs; a.Qs = nullptr; a.ys = ys;     // implicit process noise
+    a.sPs = Es; a.sms = gs;
+    a.ll = ll;
+    a.carry_in = table + 2 * dd + d;            // R of model b at table[b * bs_model + 2 dd + d], as launch_ll_batch_rc
+    return scan_rc_entry<double>(ctx, a, d, MODE_PKFS, 0, qslot, pmean, pvar, batch, bs_model, geom_batch, K);
+}
+
 template <typename Real>
 static int scan_rc_entry(pgps_ctx* ctx, ScanArgs<Real> sa, int d, Mode mode, int store_f, const int* qslot, Real* pmean,
-                         Real* pvar, int batch, long bs_model) {
+                         Real* pvar, int batch, long bs_model, int geom_batch, long bs_out) {
     const bool seg = mode == MODE_SEG_REDUCE || mode == MODE_SEG_FILTER || mode == MODE_SEG_SMOOTHER;
     if (d < rc::kDimMin || d > rc::kDimMax) return PGPS_E_UNSUPPORTED_DIM;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -2510,8 +2528,9 @@ static int scan_rc_entry(pgps_ctx* ctx, ScanArgs<Real> sa, int d, Mode mode, int
         const long cap = (d >= 10 && store_f && !qslot && mode == MODE_PKFS) ? 256 : 128;
         long lw = (sa.N + 4095) / 4096;
         if (lw > cap) { lw = (sa.N + 8191) / 8192; if (lw < 128) lw = 128; }     // 8192 chains, two full rounds of blocks
-        if (batch > 1) {                        // the models multiply the chains: keep about 8192 in flight
-            lw = ((long)sa.N * batch + 8191) / 8192;
+        const int gb = geom_batch > batch ? geom_batch : batch;     // (a group of a larger call keeps the call's geometry)
+        if (gb > 1) {                           // the models multiply the chains: keep about 8192 in flight
+            lw = ((long)sa.N * gb + 8191) / 8192;
             if (lw > 128) lw = 128;
         }
         a.Lw = (int)(lw < 8 ? 8 : lw > 512 ? 512 : lw);
@@ -2538,19 +2557,21 @@ static int scan_rc_entry(pgps_ctx* ctx, ScanArgs<Real> sa, int d, Mode mode, int
     const size_t dd = (size_t)d * d, nf = wc::nfilt(d), ns = wc::nsmth(d), nc = (size_t)a.nchunk;
     const size_t nbm = batch > 1 ? (size_t)batch : 1;
     if (bs_model > 0) {                                             // the batch entry point, B >= 1
-        if (mode != MODE_PKF || store_f) return PGPS_E_INVALID;     // batched: log-likelihood only
+        // batched: log-likelihood, or filter + smoother with the projected posterior (nothing per step is written)
+        if (store_f || !(mode == MODE_PKF || (mode == MODE_PKFS && qslot && bs_out > 0))) return PGPS_E_INVALID;
         a.batch = batch; a.bs_F = (long)sa.N * (long)dd; a.bs_agg = (long)(nc * nf); a.bs_model = bs_model;
         a.Rs = sa.carry_in;
+        if (mode == MODE_PKFS) { a.bs_sagg = (long)(nc * ns); a.bs_g = (long)sa.N * d; a.bs_out = bs_out; }
     }
     size_t off = 0;
     const size_t o_aggA = off;  off = rc_align(off + nbm * nc * nf * sizeof(Real));
     const size_t o_aggB = off;  off = rc_align(off + nbm * nc * nf * sizeof(Real));
-    const size_t o_sagA = off;  off = rc_align(off + nc * ns * sizeof(Real));
-    const size_t o_sagB = off;  off = rc_align(off + nc * ns * sizeof(Real));
+    const size_t o_sagA = off;  off = rc_align(off + nbm * nc * ns * sizeof(Real));
+    const size_t o_sagB = off;  off = rc_align(off + nbm * nc * ns * sizeof(Real));
     const size_t o_ll = off;    off = rc_align(off + nbm * nc * sizeof(double));
     const size_t o_cf = off;    off = rc_align(off + nf * sizeof(Real));
     const size_t o_cs = off;    off = rc_align(off + ns * sizeof(Real));
-    const size_t o_L = off;     if (mode != MODE_PKF) off = rc_align(off + (size_t)sa.N * dd * sizeof(Real));
+    const size_t o_L = off;     if (mode != MODE_PKF) off = rc_align(off + nbm * (size_t)sa.N * dd * sizeof(Real));
     // segments: the smoothing elements wait in scratch until the smoother phase brings sms / sPs
     const size_t o_E = off;     if (seg) off = rc_align(off + (size_t)sa.N * dd * sizeof(Real));
     const size_t o_g = off;     if (seg) off = rc_align(off + (size_t)sa.N * d * sizeof(Real));
@@ -2570,7 +2591,7 @@ static int scan_rc_entry(pgps_ctx* ctx, ScanArgs<Real> sa, int d, Mode mode, int
         sg.carry_rec = (Real*)(base + o_cf); sg.cb_rec = (Real*)(base + o_cs);
         return rc::scan_rc_seg(ctx, d, a, mode, aggA, aggB, sagA, sagB, sg, sa.ll);
     }
-    return rc::scan_rc(ctx, d, a, mode, aggA, aggB, sagA, sagB, sa.ll);
+    return rc::scan_rc(ctx, d, a, mode, aggA, aggB, sagA, sagB, sa.ll, geom_batch);
 }
 
 // ====================================================================================================

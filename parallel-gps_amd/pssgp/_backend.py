@@ -125,6 +125,18 @@ def _declare(lib):
     for dev in ("", "_dev"):
         getattr(lib, f"pgps_lti_predict_cov{dev}_f64").argtypes = [P, c_long, c_long, c_int, P, P, P, c_double, P, P, c_double,
                                                                   P, P, P, P]
+    if hasattr(lib, "pgps_gp_predict_batch_f64"):       # (absent from libraries built before predict_f_batch: A/B runs load those)
+        for suf in ("f64", "f32"):
+            for dev in ("", "_dev"):
+                getattr(lib, f"pgps_gp_predict_batch{dev}_{suf}").argtypes = [P, c_int, c_long, c_long, c_int, P, P, P, c_double,
+                                                                             P, P, P, P]
+        for dev in ("", "_dev"):
+            getattr(lib, f"pgps_lti_predict_batch{dev}_f64").argtypes = [P, c_int, c_long, c_long, c_int, P, P, P, c_double, P, P, P, P]
+        lib.pgps_series_gp_predict_batch_f64.argtypes = [P, c_int, c_int, P, P, P, P, P]
+        lib.pgps_series_lti_predict_batch_f64.argtypes = [P, c_int, c_int, P, P, P, P, P]
+        lib.pgps_mix_moments_dev_f64.argtypes = [P, c_int, c_long, P, P, P, P, P]
+        lib.pgps_set_batch_scratch.argtypes = [P, ctypes.c_size_t]
+        lib.pgps_set_batch_form.argtypes = [P, c_int]
     return lib
 
 
@@ -272,6 +284,16 @@ class Context:
         """Gradient calls at d <= 2: one derivative direction per model up to this many steps (-1 automatic, 0 never)."""
         if hasattr(self.lib, "pgps_set_grad_pack"):
             check(self, self.lib.pgps_set_grad_pack(self.handle, int(max_steps)), "pgps_set_grad_pack")
+
+    def set_batch_scratch(self, nbytes):
+        """Scratch budget of the batched predict calls (pgps_gp_predict_batch_*): the models run in groups whose filtered
+        moments and scan records fit it; 0 = the default.  A model's result does not depend on it."""
+        check(self, self.lib.pgps_set_batch_scratch(self.handle, ctypes.c_size_t(int(nbytes))), "pgps_set_batch_scratch")
+
+    def set_batch_form(self, form):
+        """Launch form of the fused batched predict: 0 = automatic, 1 = one workgroup per model (one launch), 2 = three
+        launches of (workgroups, models) grids."""
+        check(self, self.lib.pgps_set_batch_form(self.handle, int(form)), "pgps_set_batch_form")
 
     def set_rc_scan(self, mode):
         """Scans of the chain totals (row- / quad-cooperative families): -1 automatic, 0 one launch per level, 1 blocked."""
@@ -1057,6 +1079,31 @@ class Series:
                   "pgps_series_gp_predict_f64")
         return mean, var, self._ll.value
 
+    def _predict_batch(self, name, packed, d, mix):
+        B = packed.shape[0]
+        rows = 1 if mix is not None else B
+        mean, var, ll = np.empty((rows, self.K), np.float64), np.empty((rows, self.K), np.float64), np.empty(B, np.float64)
+        wv = None if mix is None else _prep(mix, np.float64, (B,))
+        with self.ctx.lock:
+            check(self.ctx, getattr(self.ctx.lib, name)(self.handle, B, d, _ptr(packed), _ptr(wv), _ptr(mean), _ptr(var), _ptr(ll)),
+                  name)
+        if mix is not None:
+            return None, None, ll, (mean[0], var[0])
+        return mean, var, ll, None
+
+    def gp_predict_batch(self, models, mix=None):
+        """B fused models at the query grid of set_queries() in one set of launches (pgps_series_gp_predict_batch_f64):
+        (mean (B, K), var (B, K), ll (B,), None); with `mix` (B normalised weights) the (B, K) results stay on the device
+        and (None, None, ll, (mixture mean (K,), mixture variance (K,))) comes back."""
+        packed, d = _gp_rows(models)
+        return self._predict_batch("pgps_series_gp_predict_batch_f64", packed, d, mix)
+
+    def lti_predict_batch(self, models, mix=None):
+        """The same for B general LTI models [(F, Pinf, H, R)] of one state dimension 2 .. 16
+        (pgps_series_lti_predict_batch_f64): the models side by side on the row-cooperative kernels, one copy back."""
+        table, d = _lti_table(models)
+        return self._predict_batch("pgps_series_lti_predict_batch_f64", table, d, mix)
+
     def close(self):
         h, self.handle = getattr(self, "handle", None), None
         if h and self.ctx is not None and getattr(self.ctx.handle, "value", None):
@@ -1105,6 +1152,24 @@ def lti_ll_batch(models, ts, ys, t0=0.0, device=0):
     return out
 
 
+def _gp_rows(models):
+    """(B x [lam | N1 | N2 | Pinf | H | R] float64 table, d) of a list of (form=(lam, N1, N2), Pinf, H, R), one state dimension."""
+    if isinstance(models, np.ndarray):          # already a table (StateSpaceGP._matern_table): 6, 16, 32 columns at d = 1, 2, 3
+        d = {6: 1, 16: 2, 32: 3}.get(models.shape[1] if models.ndim == 2 else -1)
+        if d is None:
+            raise ValueError(f"a model table has 6, 16 or 32 columns (d = 1, 2, 3), got shape {models.shape}")
+        return np.ascontiguousarray(models, dtype=np.float64), d
+    d = np.asarray(models[0][0][1]).shape[0]
+    rows = []
+    for (lam, N1, N2), Pinf, H, R in models:
+        if np.asarray(N1).shape[0] != d:
+            raise ValueError("all models of a batch must have the same state dimension")
+        rows.append(np.concatenate([[float(lam)], np.asarray(N1, np.float64).reshape(-1), np.asarray(N2, np.float64).reshape(-1),
+                                    np.asarray(Pinf, np.float64).reshape(-1), np.asarray(H, np.float64).reshape(-1),
+                                    [float(R)]]))
+    return np.ascontiguousarray(np.stack(rows), dtype=np.float64), d
+
+
 def gp_ll_batch(models, ts, ys, t0=0.0, device=0):
     """Log-likelihoods of B models over one series (pgps_gp_ll_batch_*).
 
@@ -1116,19 +1181,147 @@ def gp_ll_batch(models, ts, ys, t0=0.0, device=0):
     ys_a = _prep(ys, dtype, (-1,))
     if ys_a.shape[0] != ts_a.shape[0]:
         raise ValueError(f"observations has {ys_a.shape[0]} rows, the series {ts_a.shape[0]} steps")
-    d = np.asarray(models[0][0][1]).shape[0]
-    rows = []
-    for (lam, N1, N2), Pinf, H, R in models:
-        if np.asarray(N1).shape[0] != d:
-            raise ValueError("all models of a batch must have the same state dimension")
-        rows.append(np.concatenate([[float(lam)], np.asarray(N1, np.float64).reshape(-1), np.asarray(N2, np.float64).reshape(-1),
-                                    np.asarray(Pinf, np.float64).reshape(-1), np.asarray(H, np.float64).reshape(-1),
-                                    [float(R)]]))
-    packed = np.ascontiguousarray(np.stack(rows), dtype=np.float64)
+    packed, d = _gp_rows(models)
     out = np.zeros(len(models), np.float64)
     get_context(device).call(f"pgps_gp_ll_batch_{suf}", c_int(len(models)), c_long(ts_a.shape[0]), c_int(d), _ptr(packed),
                              _ptr(ts_a), c_double(float(t0)), _ptr(ys_a), _ptr(out))
     return out
+
+
+def gp_predict_batch(models, ts, ys, tq, t0=0.0, device=0, mix=None):
+    """predict_f of B fused (Matern-family, d <= 3) models over one series and one query grid in one set of launches
+    (pgps_gp_predict_batch_*): one merge of the sorted `ts` (N) and `tq` (K), B filters + smoothers + projections.
+    `models` as gp_ll_batch takes them.  Returns (mean (B, K), var (B, K), ll (B,), None).  With `mix` (B normalised
+    weights; float64 series) the (B, K) results stay on the device, k_mix_moments reduces them there and
+    (None, None, ll, (mixture mean (K,), mixture variance (K,))) comes back."""
+    ts_a = np.asarray(ts)
+    dtype = ts_a.dtype if ts_a.dtype in (np.float32, np.float64) else np.dtype(np.float64)
+    suf, _ = _suffix(dtype)
+    ts_a = _prep(ts_a, dtype, (-1,))
+    ys_a = _prep(ys, dtype, (-1,))
+    tq_a = _prep(tq, dtype, (-1,))
+    N, K = ts_a.shape[0], tq_a.shape[0]
+    if ys_a.shape[0] != N:
+        raise ValueError(f"observations has {ys_a.shape[0]} rows, the series {N} steps")
+    packed, d = _gp_rows(models)
+    B = packed.shape[0]
+    ctx = get_context(device)
+    ll = np.zeros(B, np.float64)
+    if mix is None or dtype != np.float64:
+        mean, var = np.empty((B, K), dtype), np.empty((B, K), dtype)
+        ctx.call(f"pgps_gp_predict_batch_{suf}", c_int(B), c_long(N), c_long(K), c_int(d), _ptr(packed), _ptr(ts_a), _ptr(ys_a),
+                 c_double(float(t0)), _ptr(tq_a), _ptr(mean), _ptr(var), _ptr(ll))
+        if mix is None:
+            return mean, var, ll, None
+        return None, None, ll, mix_moments(mean, var, mix, device=device)
+    wv = _prep(mix, np.float64, (B,))
+    mm, mv = np.empty(K, np.float64), np.empty(K, np.float64)
+    bufs = []
+    with ctx.lock:
+        try:
+            for nbytes in (8 * N, 8 * N, 8 * K, 8 * B * K, 8 * B * K, 8 * B, 8 * B, 8 * K, 8 * K):
+                bufs.append(ctx.malloc(max(nbytes, 8)))
+            dts, dys, dtq, dmean, dvar, dll, dw, dmm, dmv = (c_void_p(b) for b in bufs)
+            ctx.h2d(bufs[0], ts_a)
+            ctx.h2d(bufs[1], ys_a)
+            ctx.h2d(bufs[2], tq_a)
+            ctx.h2d(bufs[6], wv)
+            ctx.call("pgps_gp_predict_batch_dev_f64", c_int(B), c_long(N), c_long(K), c_int(d), _ptr(packed), dts, dys,
+                     c_double(float(t0)), dtq, dmean, dvar, dll)
+            ctx.call("pgps_mix_moments_dev_f64", c_int(B), c_long(K), dmean, dvar, dw, dmm, dmv)
+            ctx.d2h(mm, bufs[7])
+            ctx.d2h(mv, bufs[8])
+            ctx.d2h(ll, bufs[5])
+        finally:
+            for b in bufs:
+                ctx.free(b)
+    return None, None, ll, (mm, mv)
+
+
+def lti_predict_batch(models, ts, ys, tq, t0=0.0, device=0, mix=None):
+    """predict_f of B general LTI models [(F, Pinf, H, R)] (one state dimension, 2 .. 16) over one series and one query grid
+    (pgps_lti_predict_batch_f64): one merge, the models side by side on the row-cooperative kernels, one copy back.  Returns
+    (mean (B, K), var (B, K), ll (B,), None), or with `mix` (None, None, ll, mixture moments) reduced by mix_moments."""
+    table, d = _lti_table(models)
+    ts_a = _prep(ts, np.float64, (-1,))
+    ys_a = _prep(ys, np.float64, (-1,))
+    tq_a = _prep(tq, np.float64, (-1,))
+    N, K, B = ts_a.shape[0], tq_a.shape[0], table.shape[0]
+    if ys_a.shape[0] != N:
+        raise ValueError(f"observations has {ys_a.shape[0]} rows, the series {N} steps")
+    mean, var, ll = np.empty((B, K), np.float64), np.empty((B, K), np.float64), np.zeros(B, np.float64)
+    get_context(device).call("pgps_lti_predict_batch_f64", c_int(B), c_long(N), c_long(K), c_int(d), _ptr(table), _ptr(ts_a),
+                             _ptr(ys_a), c_double(float(t0)), _ptr(tq_a), _ptr(mean), _ptr(var), _ptr(ll))
+    if mix is None:
+        return mean, var, ll, None
+    return None, None, ll, mix_moments(mean, var, mix, device=device)
+
+
+def lti_predict_stream(models, ts, ys, tq, t0=0.0, device=0):
+    """predict_f of several general LTI models of ANY supported dimension (2 .. 32; the way for 17 .. 32, e.g. the
+    reference's CO2 kernel), one ASYNCHRONOUS device predict each (pgps_lti_predict_dev_f64), enqueued as LtiLlStream
+    enqueues likelihoods: series and query grid uploaded once, results read once.  (mean (B, K), var (B, K), ll (B,))."""
+    ts_a = _prep(ts, np.float64, (-1,))
+    ys_a = _prep(ys, np.float64, (-1,))
+    tq_a = _prep(tq, np.float64, (-1,))
+    N, K, B = ts_a.shape[0], tq_a.shape[0], len(models)
+    mean, var, ll = np.empty((B, K), np.float64), np.empty((B, K), np.float64), np.empty(B, np.float64)
+    ctx = Context(device)               # (a context of its own, as LtiLlStream: the evaluations keep scratch between calls)
+    bufs = []
+    try:
+        for nbytes in (8 * N, 8 * N, 8 * K, 8 * B * K, 8 * B * K, 8 * B):
+            bufs.append(ctx.malloc(nbytes))
+        ctx.h2d(bufs[0], ts_a)
+        ctx.h2d(bufs[1], ys_a)
+        ctx.h2d(bufs[2], tq_a)
+        for b, (F, Pinf, H, R) in enumerate(models):
+            F, Pinf, H, d = _lti_model(F, Pinf, H)
+            ctx.call("pgps_lti_predict_dev_f64", c_long(N), c_long(K), c_int(d), _ptr(F), _ptr(Pinf), _ptr(H), c_double(float(R)),
+                     c_void_p(bufs[0]), c_void_p(bufs[1]), c_double(float(t0)), c_void_p(bufs[2]),
+                     c_void_p(bufs[3] + 8 * K * b), c_void_p(bufs[4] + 8 * K * b), c_void_p(bufs[5] + 8 * b))
+        ctx.d2h(mean, bufs[3])
+        ctx.d2h(var, bufs[4])
+        ctx.d2h(ll, bufs[5])
+    finally:
+        try:
+            for p in bufs:
+                ctx.free(p)
+        finally:
+            ctx.close()
+    return mean, var, ll
+
+
+def mix_moments(mean, var, weights=None, device=0):
+    """Moments of the mixture sum_b w_b N(mean_b, var_b) on the device (pgps_mix_moments_dev_f64, fp64): mean, var (B, K)
+    host arrays, `weights` (B,) used as given (None: 1 / B each).  mix = sum_b w_b mean_b, then
+    var = sum_b w_b (var_b + (mean_b - mix)^2): two passes, every term of the variance non-negative."""
+    mean_a = _prep(mean, np.float64)
+    var_a = _prep(var, np.float64, mean_a.shape)
+    if mean_a.ndim != 2:
+        raise ValueError(f"mean must be (B, K), got {mean_a.shape}")
+    B, K = mean_a.shape
+    wv = None if weights is None else _prep(weights, np.float64, (B,))
+    mm, mv = np.empty(K, np.float64), np.empty(K, np.float64)
+    if K == 0:
+        return mm, mv
+    ctx = get_context(device)
+    bufs = []
+    with ctx.lock:
+        try:
+            for nbytes in (8 * B * K, 8 * B * K, 8 * B, 8 * K, 8 * K):
+                bufs.append(ctx.malloc(nbytes))
+            ctx.h2d(bufs[0], mean_a)
+            ctx.h2d(bufs[1], var_a)
+            if wv is not None:
+                ctx.h2d(bufs[2], wv)
+            ctx.call("pgps_mix_moments_dev_f64", c_int(B), c_long(K), c_void_p(bufs[0]), c_void_p(bufs[1]),
+                     c_void_p(bufs[2]) if wv is not None else None, c_void_p(bufs[3]), c_void_p(bufs[4]))
+            ctx.d2h(mm, bufs[3])
+            ctx.d2h(mv, bufs[4])
+        finally:
+            for b in bufs:
+                ctx.free(b)
+    return mm, mv
 
 
 def pack_grad_model(blocks):

@@ -238,6 +238,35 @@ def sunspot_map(data_dir, n_training=3200, noise_variance=10., n_interp_factor=3
                 mean_range=[float(mean.min()), float(mean.max())], max_std=float(np.sqrt(var.max())))
 
 
+def sunspot_posterior_predictive(data_dir, n_training=3000, n_draws=None, n_interp=2000, noise_variance=10., mcmc="HMC",
+                                 n_samples=1000, n_burnin=100, step_size=0.1, n_leapfrogs=10, np_seed=666, parallel=True):
+    """sunspot/mcmc.py:78-97 without the plot: the chain over the Matern-3/2 model's three parameters, then predict_f at
+    `n_draws` of its samples -- drawn with replacement by RandomState(np_seed) after the interpolation times, as the
+    reference draws its ten; None = every kept sample, each once -- on n_interp sorted uniform times over the training
+    range, in ONE predict_f_batch call.  Returns the curves (n_draws, n_interp), the moments of their equal-weight mixture
+    (the posterior predictive averaged over the draws, by the law of total variance), the two-standard-deviation band and
+    the seconds each stage took (the mixture is a second predict_f_batch call: its seconds include another filter +
+    smoother pass over all draws, with 2 n_interp numbers coming back instead of the curves)."""
+    t, y = load_sunspots(data_dir, n_training)
+    gp = StateSpaceGP((t, y), sunspot_covariance(), noise_variance, parallel=parallel)
+    tic = time.perf_counter()
+    samples, acc = run_chain(gp, mcmc, sunspot_priors(noise_variance), (), n_samples, n_burnin, step_size, n_leapfrogs)
+    chain_seconds = time.perf_counter() - tic
+    rng = np.random.RandomState(np_seed)
+    tq = np.sort(rng.uniform(t[0, 0], t[-1, 0], n_interp))[:, None]
+    rows = samples if n_draws is None else samples[rng.choice(samples.shape[0], n_draws, replace=True)]
+    tic = time.perf_counter()
+    means, variances = gp.predict_f_batch(tq, rows)
+    curves_seconds = time.perf_counter() - tic
+    tic = time.perf_counter()
+    mean, var = gp.predict_f_batch(tq, rows, reduce="mixture")
+    mixture_seconds = time.perf_counter() - tic
+    sd = np.sqrt(np.maximum(var[:, 0], 0.0))
+    return dict(times=tq[:, 0], thetas=rows, curves=means[:, :, 0], curve_variances=variances[:, :, 0], mean=mean[:, 0],
+                variance=var[:, 0], band=(mean[:, 0] - 2.0 * sd, mean[:, 0] + 2.0 * sd), acceptance=acc,
+                seconds=dict(chain=chain_seconds, curves=curves_seconds, mixture=mixture_seconds))
+
+
 def co2_hmc(data_dir, n_training=3192, qp_order=3, noise_variance=0.05, n_samples=1000, n_burnin=100, step_size=0.01,
             n_leapfrogs=10, mcmc="HMC"):
     t, y = load_co2(data_dir, n_training)
@@ -258,6 +287,11 @@ def main(argv=None):
     s.add_argument("--data-dir", required=True)
     s.add_argument("--n-training", type=int, default=3200)
     s.add_argument("--noise-variance", type=float, default=10.)
+    q = sub.add_parser("sunspot-predictive")
+    q.add_argument("--data-dir", required=True)
+    q.add_argument("--n-training", type=int, default=3000)
+    q.add_argument("--n-draws", type=int, default=None)
+    q.add_argument("--n-samples", type=int, default=1000)
     c = sub.add_parser("co2-hmc")
     c.add_argument("--data-dir", required=True)
     c.add_argument("--n-training", type=int, default=3192)
@@ -270,6 +304,12 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.cmd == "sunspot-map":
         print(json.dumps(sunspot_map(args.data_dir, args.n_training, args.noise_variance)))
+    elif args.cmd == "sunspot-predictive":
+        out = sunspot_posterior_predictive(args.data_dir, args.n_training, args.n_draws, n_samples=args.n_samples)
+        print(json.dumps(dict(n_training=args.n_training, draws=int(out["curves"].shape[0]), points=int(out["times"].shape[0]),
+                              seconds={k: round(v, 4) for k, v in out["seconds"].items()}, acceptance=out["acceptance"],
+                              mean_range=[float(out["mean"].min()), float(out["mean"].max())],
+                              max_std=float(np.sqrt(out["variance"].max())))))
     else:
         print(json.dumps(co2_hmc(args.data_dir, args.n_training, args.qp_order, args.noise_variance, args.n_samples,
                                  args.n_burnin, args.step_size, mcmc=args.mcmc)))

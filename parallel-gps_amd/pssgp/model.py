@@ -7,6 +7,8 @@ results are numpy arrays; hyper-parameters are plain floats (no GPflow `Paramete
 gradient of the log-likelihood comes from `log_likelihood_and_grad` (forward-mode duals inside
 the scan kernels) instead of TensorFlow autodiff.
 """
+import contextlib
+
 import numpy as np
 
 from . import config
@@ -951,38 +953,51 @@ class StateSpaceGP:
             grad[i] = (4.0 * d2 - d1) / 3.0
         return float(lls[0]), grad
 
-    @_public_evaluation
-    def log_likelihood_batch(self, thetas):
-        """Marginal log-likelihoods at B hyper-parameter settings in one call: `thetas` is (B, P) in the
-        order of `trainable_parameters()`.  The B filters share the series and run side by side on
-        the GPU (pgps_gp_ll_batch_*) -- the evaluation pattern of the reference's HMC / grid-search
-        drivers (pssgp/experiments/*/mcmc.py), which loop over maximum_log_likelihood_objective."""
-        if not self.parallel:
-            raise NotImplementedError("batched evaluation runs on the parallel (HIP) path: construct with parallel=True")
-        from . import _backend
-        thetas = np.atleast_2d(np.asarray(thetas, np.float64))
+    def _check_thetas(self, thetas):
+        """`thetas` as a float64 (B, P) array (one setting may be given as a vector) and the model's trainable parameters."""
+        thetas = np.asarray(thetas, np.float64)
+        if thetas.ndim == 1:
+            thetas = thetas[None, :]
         params = self.trainable_parameters()
-        if thetas.shape[1] != len(params):
-            raise ValueError(f"thetas has {thetas.shape[1]} columns, the model {len(params)} trainable parameters")
+        if thetas.ndim != 2 or thetas.shape[1] != len(params):
+            raise ValueError(f"thetas has shape {thetas.shape}, the model {len(params)} trainable parameters: expected (B, {len(params)})")
+        return thetas, params
+
+    @staticmethod
+    @contextlib.contextmanager
+    def _parameters_restored(params):
+        """The values of `params` at entry are assigned back on every exit path."""
         saved = [getattr(o, n) for o, n in params]
-        models, general = [], []
-        ts, Y = self.data
-        stream = None                   # state dimensions 17..32: asynchronous single evaluations, see below
         try:
+            yield
+        finally:
+            for (o, n), v in zip(params, saved):
+                setattr(o, n, v)
+
+    def _each_setting(self, thetas, visit):
+        """The host half of a batched evaluation, shared by log_likelihood_batch and predict_f_batch: validates `thetas`
+        (B, P), assigns each row to the model in turn and calls visit(b, form, F, P0, H) with the row's SDE -- `form` its
+        nilpotent form (lam, N1, N2) or None -- and restores the model's own parameters on every exit path.  Economies:
+        settings that differ in the noise only share one SDE; for a single Matern / RBF kernel the variance is a scaling
+        of Pinf and a nearby lengthscale a scaling of time, so one SDE is built per lengthscale neighbourhood."""
+        from . import _backend
+        thetas, params = self._check_thetas(thetas)
+        with self._parameters_restored(params):
             memo = {}                   # kernel parameters -> its SDE: settings that differ in the noise only share it
+            first_with = {}             # the parameters after the variance -> the first setting that had them
             from .kernels import Matern12, Matern32, Matern52, RBF
             leaf_variance = isinstance(self.kernel, (Matern12, Matern32, Matern52, RBF)) and params[0] == (self.kernel, "variance")
-            for row in thetas:
+            for b, row in enumerate(thetas):
                 for (o, n), v in zip(params, row):
                     setattr(o, n, float(v))
                 key = tuple(float(v) for v in row[:-1])
                 if key not in memo and leaf_variance and key[0] != 0.0:
                     # a single Matern / RBF kernel: F, H do not depend on its variance and Pinf is linear in it
                     # (balance_ss normalises L and H, q carries the scale) -- one SDE per lengthscale
-                    for other, (fo, Fo, Po, Ho) in list(memo.items()):
-                        if other[1:] == key[1:] and other[0] != 0.0:
-                            memo[key] = (fo, Fo, Po * (key[0] / other[0]), Ho)
-                            break
+                    other = first_with.get(key[1:])          # (the first setting built with these other parameters)
+                    if other is not None:
+                        fo, Fo, Po, Ho = memo[other]
+                        memo[key] = (fo, Fo, Po * (key[0] / other[0]), Ho)
                 if key not in memo and leaf_variance and key[0] != 0.0 and len(key) == 2 and key[1] > 0.0:
                     # ... and its lengthscale is a scaling of time: k(tau / l).  The state-space model at lengthscale l is
                     # the one at l0 with F multiplied by l0 / l (same Pinf / variance, same H) -- the same model as
@@ -1000,29 +1015,50 @@ class StateSpaceGP:
                     sde = self.kernel.get_sde()
                     memo[key] = (_backend.nilpotent_form(sde.F), np.asarray(sde.F, np.float64), np.asarray(sde.P0, np.float64),
                                  np.asarray(sde.H, np.float64).reshape(-1))
+                if key[0] != 0.0:
+                    first_with.setdefault(key[1:], key)
                 form, F, P0, H = memo[key]
-                if form is not None:
-                    models.append((form, P0, H, self.noise_variance))
-                d = F.shape[0]
-                if _backend.LTI_BATCH_DIM_MAX < d <= _backend.LTI_DIM_MAX:
-                    # one device evaluation per setting on the wave-cooperative kernels, enqueued as soon as its model
-                    # exists: the device runs setting i while the host builds the SDE of setting i + 1
-                    if stream is None:
-                        stream = _backend.LtiLlStream(ts.reshape(-1), Y.reshape(-1), thetas.shape[0])
-                    stream.push(F, P0, H, self.noise_variance)
-                    continue
-                # kernels without the closed-form discretisation (RBF, Periodic, sums, products): general-LTI batch
-                general.append((F, P0, H, self.noise_variance))
-            if stream is not None:
-                if stream.count != thetas.shape[0]:
+                visit(b, form, F, P0, H)
+        return thetas.shape[0]
+
+    @_public_evaluation
+    def log_likelihood_batch(self, thetas):
+        """Marginal log-likelihoods at B hyper-parameter settings in one call: `thetas` is (B, P) in the
+        order of `trainable_parameters()`.  The B filters share the series and run side by side on
+        the GPU (pgps_gp_ll_batch_*) -- the evaluation pattern of the reference's HMC / grid-search
+        drivers (pssgp/experiments/*/mcmc.py), which loop over maximum_log_likelihood_objective."""
+        if not self.parallel:
+            raise NotImplementedError("batched evaluation runs on the parallel (HIP) path: construct with parallel=True")
+        from . import _backend
+        models, general = [], []
+        ts, Y = self.data
+        stream = [None]                 # state dimensions 17..32: asynchronous single evaluations, see below
+        n_rows = np.atleast_2d(np.asarray(thetas)).shape[0]
+
+        def visit(b, form, F, P0, H):
+            if form is not None:
+                models.append((form, P0, H, self.noise_variance))
+            d = F.shape[0]
+            if _backend.LTI_BATCH_DIM_MAX < d <= _backend.LTI_DIM_MAX:
+                # one device evaluation per setting on the wave-cooperative kernels, enqueued as soon as its model
+                # exists: the device runs setting i while the host builds the SDE of setting i + 1
+                if stream[0] is None:
+                    stream[0] = _backend.LtiLlStream(ts.reshape(-1), Y.reshape(-1), n_rows)
+                stream[0].push(F, P0, H, self.noise_variance)
+                return
+            # kernels without the closed-form discretisation (RBF, Periodic, sums, products): general-LTI batch
+            general.append((F, P0, H, self.noise_variance))
+
+        try:
+            n_rows = self._each_setting(thetas, visit)
+            if stream[0] is not None:
+                if stream[0].count != n_rows:
                     raise ValueError("all settings of a batch must give the same state dimension")
-                out, stream = stream.finish(), None
+                out, stream[0] = stream[0].finish(), None
                 return out
         finally:
-            for (o, n), v in zip(params, saved):
-                setattr(o, n, v)
-            if stream is not None:
-                stream.close()
+            if stream[0] is not None:
+                stream[0].close()
         if len(models) == len(general):
             return _backend.gp_ll_batch(models, ts.reshape(-1), Y.reshape(-1))
         d = general[0][0].shape[0]
@@ -1033,6 +1069,206 @@ class StateSpaceGP:
             return _backend.lti_ll_batch(general, ts.reshape(-1), Y.reshape(-1))
         raise NotImplementedError(f"batched evaluation covers the Matern family and state dimensions "
                                   f"{_backend.LTI_DIM_MIN}..{_backend.LTI_DIM_MAX}; this kernel has d = {d}")
+
+    @staticmethod
+    def _mixture_weights(weights, B):
+        """`weights` normalised to sum 1 (None: equal), validated: one per setting, none negative, not all zero."""
+        if weights is None:
+            return np.full(B, 1.0 / B)
+        w = np.asarray(weights, np.float64).reshape(-1)
+        if w.shape[0] != B:
+            raise ValueError(f"weights has {w.shape[0]} entries, thetas {B} rows")
+        if not np.all(np.isfinite(w)) or np.any(w < 0.0) or not w.sum() > 0.0:
+            raise ValueError("weights must be finite, non-negative and not all zero")
+        return w / w.sum()
+
+    @staticmethod
+    def _mix_moments_host(mean, var, w):
+        """Moments of sum_b w_b N(mean_b, var_b), (B, K) -> (K,), (K,): the two-pass form, every term of the variance
+        non-negative (what k_mix_moments computes on the device)."""
+        mix = np.sum(w[:, None] * mean, axis=0)
+        return mix, np.sum(w[:, None] * (var + (mean - mix[None, :]) ** 2), axis=0)
+
+    @_public_evaluation
+    def predict_f_batch(self, Xnew, thetas, return_log_likelihood=False, reduce=None, weights=None):
+        """predict_f at B hyper-parameter settings over the same series and query grid: `thetas` is (B, P) in the order of
+        `trainable_parameters()`.  Returns means (B, K, 1) and variances (B, K, 1) -- row b what predict_f(Xnew) returns
+        with row b assigned to the model -- and, with return_log_likelihood=True, the B training log-likelihoods (the
+        filter pass has them).  reduce="mixture": the moments (K, 1), (K, 1) of sum_b w_b N(mean_b, var_b) instead, w =
+        `weights` normalised (None: equal): mean = sum_b w_b mean_b, var = sum_b w_b (var_b + (mean_b - mean)^2) -- the
+        posterior predictive averaged over the draws of a chain (pssgp/experiments/sunspot/mcmc.py:78-97 loops predict_f
+        over ten of them).  Xnew in any order, repeated times allowed.  The model's own parameters are restored on every
+        exit path.
+
+        parallel=True: a single Matern kernel (fp64 and float32 series) runs the B filters, smoothers and projections in
+        one set of launches (pgps_gp_predict_batch_*, on the resident series from the model's second evaluation), and the
+        mixture is reduced on the device (k_mix_moments): 2 K numbers come back.  Every other kernel (RBF, Periodic, sums,
+        products) with 2 <= d <= 16 runs on the row-cooperative kernels, the B models side by side in the launches of one
+        predict (pgps_lti_predict_batch_f64); d = 17 .. 32 takes asynchronous single calls; the SDEs are built as
+        log_likelihood_batch builds them.  parallel=False: a host loop over the sequential path
+        (_predict_f_host: fp64, discretised on the host), any kernel, no device."""
+        if reduce not in (None, "mixture"):
+            raise ValueError(f"reduce must be None or 'mixture', got {reduce!r}")
+        thetas, params = self._check_thetas(thetas)
+        B = thetas.shape[0]
+        if reduce is None and weights is not None:
+            raise ValueError("weights are the mixture's: pass reduce='mixture'")
+        w = self._mixture_weights(weights, B) if reduce == "mixture" else None
+        dtype = config.default_float()
+        xq = np.asarray(Xnew, dtype=dtype).reshape(-1)
+        K = xq.shape[0]
+        if K <= 1 or np.all(xq[1:] > xq[:-1]):
+            tq, inverse = xq, None                                # already sorted, each time once
+        else:
+            tq, inverse = np.unique(xq, return_inverse=True)
+        rows = (lambda a: a) if inverse is None else (lambda a: a[..., inverse])
+        device = self.parallel and K > 0
+        if device and getattr(self, "_series", None) is None:     # (a resident series was checked when it was made)
+            squeezed_ts = self.data[0].reshape(-1)
+            device = squeezed_ts.size > 0 and bool(np.all(np.diff(squeezed_ts) >= 0))
+        mixed = None
+        if not device:
+            mean, var, lls = self._predict_f_batch_loop(tq, thetas, params, return_log_likelihood or K == 0)
+        else:
+            mean, var, lls, mixed = self._predict_f_batch_device(tq, thetas, params, w, return_log_likelihood)
+        if reduce == "mixture":
+            if mixed is None:
+                mixed = self._mix_moments_host(np.asarray(mean, np.float64), np.asarray(var, np.float64), w)
+            out = (rows(mixed[0])[:, None].astype(dtype, copy=False), rows(mixed[1])[:, None].astype(dtype, copy=False))
+        else:
+            out = (rows(mean)[:, :, None].astype(dtype, copy=False), rows(var)[:, :, None].astype(dtype, copy=False))
+        if return_log_likelihood:
+            out = out + (np.asarray(lls, dtype),)
+        return out
+
+    def _predict_f_host(self, tq):
+        """predict_f and the training log-likelihood at the model's current setting on the host alone, fp64: merge,
+        discretisation (_host_discretise), sequential filter + smoother, projection at the (sorted) query rows -- the host
+        half of _predict_f_full_cov without the covariance.  (mean (K,), var (K,), ll): the query rows are missing
+        observations and add nothing to the log-likelihood."""
+        ts, ys = self.data
+        squeezed_ts = np.asarray(ts, np.float64).reshape(-1)
+        nan_ys = np.full((tq.shape[0], ys.shape[1]), np.nan, dtype=np.float64)
+        all_ts, all_ys, all_flags = _merge_sorted(
+            squeezed_ts, np.asarray(tq, np.float64), (np.asarray(ys, np.float64), nan_ys),
+            (np.zeros(squeezed_ts.shape, dtype=bool), np.ones(tq.shape, dtype=bool)))
+        sde = self.kernel.get_sde()
+        h = np.asarray(sde.H, np.float64).reshape(-1)
+        P0 = np.asarray(sde.P0, np.float64)
+        Fs, Qs = _host_discretise(sde.F, P0, all_ts)
+        ssm = (P0, Fs, Qs, h[None, :], np.reshape(np.float64(self.noise_variance), (1, 1)))
+        fms, fPs, ll, mps, Pps = kf(ssm, all_ys, return_loglikelihood=True, return_predicted=True)
+        sms, sPs = sequential.ks(ssm, fms, fPs, mps, Pps)
+        return sms[all_flags] @ h, np.einsum("i,nij,j->n", h, sPs[all_flags], h), float(ll)
+
+    def _predict_f_batch_loop(self, tq, thetas, params, want_ll):
+        """predict_f_batch as a loop over the settings: assign row b, predict on the sorted unique grid (and the
+        log-likelihood).  parallel=False: _predict_f_host, no device; else predict_f and the objective (kernels and series
+        the batched device calls do not take, and batches too small for them).  (B, K), (B, K), (B,) or None."""
+        B, K = thetas.shape[0], tq.shape[0]
+        dtype = config.default_float()
+        mean, var = np.zeros((B, K), dtype), np.zeros((B, K), dtype)
+        lls = np.zeros(B, dtype) if want_ll else None
+        with self._parameters_restored(params):
+            for b, row in enumerate(thetas):
+                for (o, n), v in zip(params, row):
+                    setattr(o, n, float(v))
+                if not self.parallel:
+                    mean[b], var[b], ll = self._predict_f_host(tq)
+                    if want_ll:
+                        lls[b] = ll
+                    continue
+                if K > 0:
+                    m, v = self.predict_f(tq[:, None])
+                    mean[b], var[b] = m[:, 0], v[:, 0]
+                if want_ll:
+                    lls[b] = self.maximum_log_likelihood_objective()
+        return mean, var, lls
+
+    # predict_f_batch, Matern family: settings from which the batched launches replace the loop of single predicts.  Measured
+    # (tools/predict_batch_bench.py --forms, MI355X, N = 3000, K = 2000, resident series, median [min, max] ms): B = 1 batched
+    # 0.086 [0.083, 0.111] against the loop's 0.068 [0.062, 0.111]; B = 2 0.085 [0.083, 0.104] against 0.132 [0.128, 0.140] --
+    # a call of the batch costs what ~1.3 single predicts do (profiles/predict_batch_bench.json).
+    _PREDICT_BATCH_FROM = 2
+
+    def _matern_table(self, thetas, params):
+        """The (B, 1 + 3 d^2 + d + 1) table [lam | N1 | N2 | Pinf | H | R] of a SINGLE Matern-1/2, -3/2 or -5/2 kernel at the B
+        rows (variance, lengthscales, noise variance) of `thetas`, built with array operations from _matern_forms()'
+        closed forms: no parameter is assigned and no SDE built per row (the row-by-row path costs ~12 us per setting, and
+        its search for a setting with the same lengthscale grows with B^2: 44 ms of a 45 ms call at B = 1000).  None
+        where _matern_forms() does not apply or a row is not positive."""
+        if self._matern_forms() is None or not np.all(thetas > 0.0):
+            return None
+        if [n for _, n in params] != ["variance", "lengthscales", "noise_variance"]:
+            return None
+        s2, ell, R = thetas[:, 0], thetas[:, 1], thetas[:, 2]
+        B = thetas.shape[0]
+        name = type(self.kernel).__name__
+        d = {"Matern12": 1, "Matern32": 2, "Matern52": 3}[name]
+        dd = d * d
+        table = np.zeros((B, 1 + 3 * dd + d + 1))
+        N1, N2, Pinf, H = (table[:, 1:1 + dd], table[:, 1 + dd:1 + 2 * dd], table[:, 1 + 2 * dd:1 + 3 * dd],
+                           table[:, 1 + 3 * dd:1 + 3 * dd + d])
+        if name == "Matern12":
+            lam = 1.0 / ell
+            Pinf[:, 0], H[:, 0] = s2, 1.0
+        elif name == "Matern32":
+            lam = np.sqrt(3.0) / ell
+            N1[:, 0], N1[:, 1], N1[:, 2], N1[:, 3] = lam, 1.0, -lam * lam, -lam
+            Pinf[:, 0], Pinf[:, 3] = s2, lam * lam * s2
+            H[:, 0] = 1.0
+        else:
+            P1, H1, U1, U2 = self._matern52_unit
+            lam = np.sqrt(5.0) / ell
+            N1[...] = lam[:, None] * U1.reshape(1, -1)
+            N2[...] = (lam * lam)[:, None] * U2.reshape(1, -1)
+            Pinf[...] = s2[:, None] * P1.reshape(1, -1)
+            H[...] = H1.reshape(1, -1)
+        table[:, 0], table[:, -1] = lam, R
+        return table
+
+    def _predict_f_batch_device(self, tq, thetas, params, w, want_ll):
+        """The device half of predict_f_batch (sorted series, K > 0): (mean (B, K), var (B, K), lls (B,), mixture or None)."""
+        from . import _backend
+        B = thetas.shape[0]
+        if B < self._PREDICT_BATCH_FROM and self._matern_forms() is not None:
+            return self._predict_f_batch_loop(tq, thetas, params, want_ll) + (None,)     # the loop of single calls is faster
+        ts, ys = self.data
+        t, y = ts.reshape(-1), ys.reshape(-1)
+        ser = self._device_series() if t.dtype == np.float64 else None
+        if ser is not None:
+            ser.set_queries(tq)
+        table = self._matern_table(thetas, params)
+        if table is not None:
+            if ser is not None:
+                return ser.gp_predict_batch(table, mix=w)
+            return _backend.gp_predict_batch(table, t, y, tq.astype(t.dtype), mix=w)
+        fused, general = [], []
+
+        def visit(b, form, F, P0, H):
+            if form is not None and F.shape[0] <= 3:
+                fused.append((form, P0, H, self.noise_variance))
+            general.append((F, P0, H, self.noise_variance))
+
+        self._each_setting(thetas, visit)
+        if len(fused) == B:                     # (a composite kernel whose SDE has the fused form)
+            if ser is not None:
+                return ser.gp_predict_batch(fused, mix=w)
+            return _backend.gp_predict_batch(fused, t, y, tq.astype(t.dtype), mix=w)
+        d = general[0][0].shape[0]
+        if any(g[0].shape[0] != d for g in general):
+            raise ValueError("all settings of a batch must give the same state dimension")
+        if _backend.LTI_DIM_MIN <= d <= _backend.LTI_BATCH_DIM_MAX:
+            # general-LTI kernels, fp64 arithmetic (a float32 series widened): the B models side by side on the
+            # row-cooperative kernels
+            if ser is not None and ser.has_lti:
+                return ser.lti_predict_batch(general, mix=w)
+            return _backend.lti_predict_batch(general, t, y, tq, mix=w)
+        if _backend.LTI_BATCH_DIM_MAX < d <= _backend.LTI_DIM_MAX:
+            # d = 17 .. 32 (the CO2 kernel): asynchronous single predicts, as LtiLlStream enqueues likelihoods
+            return _backend.lti_predict_stream(general, t, y, tq) + (None,)
+        # no device form for this kernel (d = 1 outside the Matern family, d > 32): the loop over predict_f
+        return self._predict_f_batch_loop(tq, thetas, params, True) + (None,)
 
     def log_posterior_density(self):
         return self.maximum_log_likelihood_objective()
