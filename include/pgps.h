@@ -320,7 +320,12 @@ int pgps_pkfs_dev_f32(pgps_ctx*, long N, int d, const float* P0, const float* Fs
  * device pointers for pgps_gp_dev_* and host pointers for pgps_gp_*.
  *   fms/fPs == NULL and sms/sPs == NULL : log-likelihood only (nothing is written per step)
  *   sms/sPs == NULL                     : filter (pkf with return_loglikelihood=True)
- *   all given                           : filter + smoother (pkfs) + log-likelihood. */
+ *   all given                           : filter + smoother (pkfs) + log-likelihood
+ *   fms/fPs == NULL, sms/sPs given      : smoother + log-likelihood without the filtered moments.  pgps_gp_f64 stages them
+ *                                         itself on every road; pgps_gp_dev_f64 takes the call only where the resident
+ *                                         launch runs it (d = 2, pgps_get_family says PGPS_FAMILY_RESIDENT): the three
+ *                                         launches hand the filtered moments to the smoother through fms / fPs and
+ *                                         answer PGPS_E_INVALID. */
 int pgps_gp_dev_f64(pgps_ctx*, long N, int d, double lam, const double* N1, const double* N2, const double* Pinf,
                     const double* H, double R, const double* ts, double t0, const double* ys, double* fms,
                     double* fPs, double* sms, double* sPs, double* ll);

@@ -1293,8 +1293,7 @@ static int gp_dev(pgps_ctx* ctx, long N, int d, double lam, const double* N1, co
     if (!ctx || N < 1 || !N1 || !Pinf || !H || !ts || !ys) return PGPS_E_INVALID;
     if (d < 1 || d > 3) return PGPS_E_UNSUPPORTED_DIM;
     if ((fms == nullptr) != (fPs == nullptr) || (sms == nullptr) != (sPs == nullptr)) return PGPS_E_INVALID;
-    if (sms && !fms) return PGPS_E_INVALID;             // the smoother reads the filtered moments back
-    if (!fms && !ll) return PGPS_E_INVALID;
+    if (!fms && !sms && !ll) return PGPS_E_INVALID;
     if ((fms && (!aligned16(fms) || !aligned16(fPs))) || (sms && (!aligned16(sms) || !aligned16(sPs))))
         return PGPS_E_INVALID;
     GpArgs<T> g{};
@@ -1316,6 +1315,7 @@ static int gp_dev(pgps_ctx* ctx, long N, int d, double lam, const double* N1, co
             return launch_resident<double, 2>(ctx, ra, true, sms != nullptr);
         }
     }
+    if (sms && !fms) return PGPS_E_INVALID;             // three launches: the smoother reads the filtered moments back
     switch (d) {
         case 1: return launch_gp<T, 1>(ctx, g, fms != nullptr, sms != nullptr);
         case 2: return launch_gp<T, 2>(ctx, g, fms != nullptr, sms != nullptr);

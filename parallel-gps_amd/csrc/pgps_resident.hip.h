@@ -16,7 +16,11 @@
 //             left, drained coalesced), log-likelihood, and the smoothing element (E, g, L) of every step
 //             (parallel.py:159-166) IN PLACE of the step's inputs: E, g in the registers F and y have left, L in
 //             the slot; lane aggregate of the elements, workgroup suffix scan, total published; then the workgroup's
-//             log-likelihood partial, while the right neighbour's total is still on its way
+//             log-likelihood partial, while the right neighbour's total is still on its way.
+//             The stores are spread under the arithmetic: the filtered P of a sub-tile (four steps per lane) leaves
+//             in groups of 3, 3, 2 wave-instructions behind the first three steps of the NEXT sub-tile, its means in
+//             one group of 4 at its own end; the L records of a sub-tile wait in registers until its P has left the
+//             slots; the last sub-tile's P leaves around the element of the chunk's last step
 //   barrier 2
 //   phase 3   fold the totals to the right, lane-serial smoothing-operator pass (parallel.py:176-184) backwards over
 //             the kept elements: sms, sPs out through the slots
@@ -40,7 +44,9 @@
 // predict that changes nothing), the element of step N - 1 is the reference's last element (0, m, P) (parallel.py:155-156)
 // with E exactly zero, the padded steps' elements (about the identity, from smth_element on F = I, Q = 0) lie to its right
 // and reach nothing as long as they are finite (tests/test_gpu_resident_skew.py: near-singular filtered P before the
-// padding), and stores beyond N are predicated off -- one code path.
+// padding), and stores beyond N are predicated off -- one code path for the arithmetic; each group of output stores
+// exists twice, for a whole wave (no predicate, the group's LDS reads issued together) and for a ragged one, behind one
+// scalar branch.
 #pragma once
 
 #include <type_traits>
@@ -161,32 +167,62 @@ __device__ __forceinline__ void res_commit(char* slots, int sb, const V4* r) {
 #pragma unroll
     for (int v = 0; v < NV; ++v) *reinterpret_cast<V4*>(base + sb * GEO::SEG + v * OPI * SLOT) = r[v];
 }
-// the owners' slots -> global (coalesced), pieces at or beyond `lim` dropped
+// A store predicate is one 32-bit compare: `lim` (res_lim32) = the bytes of the wave's span of the array that lie below N,
+// clamped to [0, 2^30] -- a span is 64 * PITCH bytes -- against the lane's offset; the piece's own offset is a scalar.
+__device__ __forceinline__ int res_lim32(long lim) { return lim < 0 ? 0 : (lim > (1L << 30) ? (1 << 30) : (int)lim); }
+// the owners' slots -> global (coalesced), pieces at or beyond `lim` dropped: pieces v0 .. v0 + nv - 1 of sub-tile `sb`
+// (one wave-instruction each: OPI owners, all G records of each)
 template <typename GEO, int SLOT, int PITCH>
-__device__ __forceinline__ void res_drain(char* __restrict__ g /*wave-uniform*/, int sb, long lim, bool full, const char* slots) {
+__device__ __forceinline__ void res_drain_part(char* __restrict__ g /*wave-uniform*/, int sb, int v0, int nv, int lim, bool full,
+                                               const char* slots) {
     const int lane = threadIdx.x & (kWave - 1);
     constexpr int NV = GEO::NV, OPI = kWave / NV;
     const char* base = slots + (lane / NV) * SLOT + (lane % NV) * 16;
     const unsigned loff = (unsigned)(lane / NV) * PITCH + (unsigned)(lane % NV) * 16u;
+    if (full) {
+        // a whole wave (one scalar branch for the group): every read is issued before the first store waits for its data
+        V4 x[NV];
 #pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const V4 x = *reinterpret_cast<const V4*>(base + sb * GEO::SEG + v * OPI * SLOT);
-        const long off = (long)sb * GEO::SEG + (long)v * OPI * PITCH + loff;
-        if (full || off < lim) *reinterpret_cast<V4*>(g + ((long)sb * GEO::SEG + (long)v * OPI * PITCH) + loff) = x;
+        for (int v = 0; v < NV; ++v)
+            if (v >= v0 && v < v0 + nv) x[v] = *reinterpret_cast<const V4*>(base + sb * GEO::SEG + v * OPI * SLOT);
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+            if (v >= v0 && v < v0 + nv) *reinterpret_cast<V4*>(g + ((long)sb * GEO::SEG + (long)v * OPI * PITCH) + loff) = x[v];
+    } else {
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            if (v < v0 || v >= v0 + nv) continue;
+            const V4 x = *reinterpret_cast<const V4*>(base + sb * GEO::SEG + v * OPI * SLOT);
+            if ((int)loff < lim - (sb * GEO::SEG + v * OPI * PITCH))
+                *reinterpret_cast<V4*>(g + ((long)sb * GEO::SEG + (long)v * OPI * PITCH) + loff) = x;
+        }
     }
+}
+// the whole sub-tile
+template <typename GEO, int SLOT, int PITCH>
+__device__ __forceinline__ void res_drain(char* __restrict__ g /*wave-uniform*/, int sb, int lim, bool full, const char* slots) {
+    res_drain_part<GEO, SLOT, PITCH>(g, sb, 0, GEO::NV, lim, full, slots);
 }
 // the means of one sub-tile: staging buffer (one sub-tile deep) -> global
 template <typename GEO, int PITCH>
-__device__ __forceinline__ void res_drain_m(char* __restrict__ g /*wave-uniform*/, int sb, long lim, bool full, const char* mst) {
+__device__ __forceinline__ void res_drain_m(char* __restrict__ g /*wave-uniform*/, int sb, int lim, bool full, const char* mst) {
     const int lane = threadIdx.x & (kWave - 1);
     constexpr int NV = GEO::NV, OPI = kWave / NV;
     const char* base = mst + (lane / NV) * GEO::STRIDE + (lane % NV) * 16;
     const unsigned loff = (unsigned)(lane / NV) * PITCH + (unsigned)(lane % NV) * 16u;
+    if (full) {
+        V4 x[NV];
 #pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const V4 x = *reinterpret_cast<const V4*>(base + v * OPI * GEO::STRIDE);
-        const long off = (long)sb * GEO::SEG + (long)v * OPI * PITCH + loff;
-        if (full || off < lim) *reinterpret_cast<V4*>(g + ((long)sb * GEO::SEG + (long)v * OPI * PITCH) + loff) = x;
+        for (int v = 0; v < NV; ++v) x[v] = *reinterpret_cast<const V4*>(base + v * OPI * GEO::STRIDE);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) *reinterpret_cast<V4*>(g + ((long)sb * GEO::SEG + (long)v * OPI * PITCH) + loff) = x[v];
+    } else {
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            const V4 x = *reinterpret_cast<const V4*>(base + v * OPI * GEO::STRIDE);
+            if ((int)loff < lim - (sb * GEO::SEG + v * OPI * PITCH))
+                *reinterpret_cast<V4*>(g + ((long)sb * GEO::SEG + (long)v * OPI * PITCH) + loff) = x;
+        }
     }
 }
 
@@ -557,7 +593,8 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
     const long wbase = ((long)tile * kBlock + wave * kWave) * LC;
     const bool full = (wbase + (long)kWave * LC <= N);                      // wave-uniform: no padding, no predicates
     constexpr int PF = LC * MAT * (int)sizeof(T), PM = LC * D * (int)sizeof(T);        // a lane's bytes of a matrix / vector array
-    const long limF = (N - wbase) * MAT * (long)sizeof(T), limM = (N - wbase) * D * (long)sizeof(T);
+    const long limF = (N - wbase) * MAT * (long)sizeof(T);
+    const int limP = res_lim32(limF), limM = res_lim32((N - wbase) * D * (long)sizeof(T));     // the output stores' predicates
 
     T h[D], P0[SYM];
     if constexpr (FUSED) {
@@ -781,34 +818,40 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
             }
         }
     }
-    // smoothing element of step k_next - 1 from the predict of step k_next (parallel.py:159-166).  k_next == N: the series'
-    // last element (0, m, P) (parallel.py:155-156) -- which is what the formulas give for F P = 0 (E = 0, g = m, L = P).
-    // Beyond N the padded steps (F = I, Q = 0) give the identity element up to rounding, to the RIGHT of an element whose
-    // E is exactly zero: they reach nothing.
-    auto element = [&](long k_next, const MC& prev, const T* mp, const T* Pp, T* FP, SE& e) {
-        const bool last = (k_next == N);
+    // smoothing element of step k0 + j_next - 1 from the predict of step k0 + j_next (parallel.py:159-166).  At step N: the
+    // series' last element (0, m, P) (parallel.py:155-156) -- which is what the formulas give for F P = 0 (E = 0, g = m,
+    // L = P).  Beyond N the padded steps (F = I, Q = 0) give the identity element up to rounding, to the RIGHT of an element
+    // whose E is exactly zero: they reach nothing.
+    const int to_end = (N - k0 < 0) ? -1 : (N - k0 > LC ? LC + 1 : (int)(N - k0));      // steps from the lane's first to step N, as far as the test needs it
+    auto element = [&](int j_next, const MC& prev, const T* mp, const T* Pp, T* FP, SE& e) {
+        const bool last = (j_next == to_end);
 #pragma unroll
         for (int q = 0; q < MAT; ++q) FP[q] = last ? T(0) : FP[q];
         smth_element(prev, mp, Pp, FP, e);
     };
+    // Drain schedule (filtered outputs requested).  A wave with a burst of stores in front of it stands still until the memory
+    // path has taken them, and with one wave per SIMD nothing else runs meanwhile; spread out, the stores leave under the
+    // arithmetic.  The means of sub-tile sb leave at its end (NV = 4 pieces; their staging buffer is one sub-tile deep).  The
+    // NVP = 8 pieces of its filtered P leave DURING sub-tile sb + 1: PPS = 3, 3, 2 behind its first three steps, none behind
+    // the fourth, which the means follow.  A piece holds all G records of OPI owners, so the slot records of sub-tile sb stay
+    // "filtered P" until the last of its pieces has been read: their L records wait in registers one sub-tile longer (Lwait).
+    // The last sub-tile's pieces go around the element of the chunk's last step, half before it and half behind, and its L
+    // records into their slots after them, before phase 3 reads them.
     const bool store_f = (a.fms != nullptr);
     char* gP = reinterpret_cast<char*>(a.fPs + wbase * MAT);
     char* gM = reinterpret_cast<char*>(a.fms + wbase * D);
-    T Lhold[MAT];               // [L | leading components of g] of a step, until the step's slot record has been drained
+    constexpr int NVP = GF::NV, PPS = (NVP + G - 2) / (G - 1);
+    T Lhold[MAT];               // [L | leading components of g] of the step before a sub-tile's first, until its slot record has been drained
+    T Lwait[G - 1][MAT];        // those of the previous sub-tile's other steps
 #pragma unroll
     for (int sb = 0; sb < S; ++sb) {
-        T Lnew[G][MAT];
+        T Lnew[G - 1][MAT];
 #pragma unroll
         for (int i = 0; i < G; ++i) {
             const int j = sb * G + i;
             T Q[SYM];
             sym_from_full<T, D>(Qn, Q);
-#ifndef PGPS_RES_NOQPF
             if (j + 1 < LC) load_rec<T, MAT>(myrec + (j + 1) * MAT, Qn);       // the next step's Q: requested a step ahead
-#endif
-#ifdef PGPS_RES_NOQPF
-            if (j + 1 < LC) load_rec<T, MAT>(myrec + (j + 1) * MAT, Qn);
-#endif
             MC prev = s;
             T mp[D], Pp[SYM], FP[MAT];
             if (j == 0) {
@@ -823,7 +866,7 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
                 if constexpr (SMOOTH) {
                     // element of step j - 1: E, g take the registers F_{j-1}, y_{j-1} have left; L waits for its slot
                     SE e, r;
-                    element(k0 + j, prev, mp, Pp, FP, e);
+                    element(j, prev, mp, Pp, FP, e);
                     smth_combine(sagg, e, r);
                     sagg = r;
 #pragma unroll
@@ -841,25 +884,34 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
             full_from_sym<T, D>(s.P, Pf);
             store_rec<T, MAT>(myrec + j * MAT, Pf);
             store_rec<T, D>(reinterpret_cast<T*>(mst + lane * GM::STRIDE) + i * D, s.m);
+            // pieces of the previous sub-tile's filtered P (in the slots since the sync at its end)
+            if (sb > 0 && store_f) res_drain_part<GF, SLOT, PF>(gP, sb - 1, i * PPS, PPS, limP, full, slots);
 #ifndef PGPS_RES_NOSB
-            __builtin_amdgcn_sched_barrier(0);          // steps stay apart: across them the scheduler only lengthens live ranges (scratch)
+            // steps stay apart: across them the scheduler only lengthens live ranges (scratch) and gathers the stores
+            __builtin_amdgcn_sched_barrier(0);
 #endif
         }
         res_wave_sync();
-        if (store_f) {
-            res_drain<GF, SLOT, PF>(gP, sb, limF, full, slots);
-            res_drain_m<GM, PM>(gM, sb, limM, full, mst);
-        }
+        if (store_f) res_drain_m<GM, PM>(gM, sb, limM, full, mst);
         res_wave_sync();
         if constexpr (SMOOTH) {
-            // L of steps 4 sb - 1 .. 4 sb + 2 into their slots (drained above; LDS keeps a wave's accesses in order)
-            if (sb > 0) store_rec<T, MAT>(myrec + (sb * G - 1) * MAT, Lhold);
+            // L of steps 4 sb - 4 .. 4 sb - 1 into their slots: every piece of that sub-tile has been read (LDS keeps a wave's
+            // accesses in order)
+            if (sb > 0) {
 #pragma unroll
-            for (int i = 0; i + 1 < G; ++i) store_rec<T, MAT>(myrec + (sb * G + i) * MAT, Lnew[i]);
+                for (int i = 0; i + 1 < G; ++i) store_rec<T, MAT>(myrec + ((sb - 1) * G + i) * MAT, Lwait[i]);
+                store_rec<T, MAT>(myrec + (sb * G - 1) * MAT, Lhold);
+            }
+#pragma unroll
+            for (int i = 0; i + 1 < G; ++i)
+#pragma unroll
+                for (int q = 0; q < MAT; ++q) Lwait[i][q] = Lnew[i][q];
         }
     }
     if constexpr (!SMOOTH) {
-        // the filter alone: the workgroup's log-likelihood partial out, one arrival; workgroup 0 sums when everyone has arrived
+        // the filter alone: the last sub-tile's pieces, then the workgroup's log-likelihood partial out, one arrival; workgroup 0
+        // sums when everyone has arrived
+        if (store_f) res_drain_part<GF, SLOT, PF>(gP, S - 1, 0, NVP, limP, full, slots);
         PGPS_RSTAMP_WAVE(1);
         PGPS_RSTAMP(5);
         const double v = ll.value();
@@ -882,14 +934,15 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
         return;
     }
     {
-        // element of the chunk's last step from the step after the chunk
+        // element of the chunk's last step from the step after the chunk, between the halves of the last sub-tile's pieces
+        if (store_f) res_drain_part<GF, SLOT, PF>(gP, S - 1, 0, NVP / 2, limP, full, slots);
         constexpr int j = LC - 1;
         T Q[SYM], mp[D], Pp[SYM], FP[MAT];
         sym_from_full<T, D>(Qh, Q);
         mat_vec<T, D>(Fh, s.m, mp);
         predict_cov<T, D>(Fh, s.P, Q, FP, Pp);
         SE e, r;
-        element(k0 + LC, s, mp, Pp, FP, e);
+        element(LC, s, mp, Pp, FP, e);
         smth_combine(sagg, e, r);
         sagg = r;
 #pragma unroll
@@ -898,6 +951,14 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
         T Lg[MAT];
 #pragma unroll
         for (int q = 0; q < MAT; ++q) Lg[q] = q < SYM ? e.L[q < SYM ? q : 0] : e.g[q < SYM ? 0 : q - SYM];
+        // (the element is computed HERE, between the two halves: without the pin it sinks below the second one)
+#pragma unroll
+        for (int q = 0; q < MAT; ++q) asm volatile("" : "+v"(Lg[q]));
+        __builtin_amdgcn_sched_barrier(0);
+        if (store_f) res_drain_part<GF, SLOT, PF>(gP, S - 1, NVP / 2, NVP - NVP / 2, limP, full, slots);
+        res_wave_sync();
+#pragma unroll
+        for (int i = 0; i + 1 < G; ++i) store_rec<T, MAT>(myrec + ((S - 1) * G + i) * MAT, Lwait[i]);
         store_rec<T, MAT>(myrec + j * MAT, Lg);
     }
     PGPS_RSTAMP_WAVE(1);
@@ -1016,7 +1077,7 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
             store_rec<T, D>(reinterpret_cast<T*>(mst + lane * GM::STRIDE) + i * D, s.m);
         }
         res_wave_sync();
-        res_drain<GF, SLOT, PF>(oP, sb, limF, full, slots);
+        res_drain<GF, SLOT, PF>(oP, sb, limP, full, slots);
         res_drain_m<GM, PM>(oM, sb, limM, full, mst);
         res_wave_sync();
     }

@@ -1,6 +1,9 @@
 """Phase stamps of the resident launch (csrc/pgps_resident.hip.h) at 2^20 steps, array and fused form, with the per-wave
 split of the reduce and Kalman-pass ends (libraries that have pgps_resident_wave_stamps).  Medians over the workgroups of
-one launch, for `--reps` launches.   PGPS_LIB=<library> python tools/res_stamps.py [--reps 3]
+one launch, for `--reps` launches.   PGPS_LIB=<library> python tools/res_stamps.py [--reps 3] [--no-filtered]
+
+--no-filtered: the fused form without the filtered outputs (fms, fPs not requested: the Kalman pass then stores nothing; the
+array entry point always returns them) -- what the pass costs without its stores.
 
 Stamps (slots of resident_stamps(), wave 0 lane 0): 0 start, 1 reduce done, 2 forward scan done (and, where the total is
 published from inside the scan, published), 3 carry in, 4 applied, 5 Kalman pass + last element done, 6 suffix scan done,
@@ -43,6 +46,7 @@ def table(st, ws):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--no-filtered", action="store_true", help="fused form only, filtered outputs not requested")
     args = ap.parse_args()
     ctx = B.get_context(0)
     kern = Matern32(variance=1.0, lengthscales=1.0)
@@ -71,13 +75,15 @@ def main():
                  c_double(float(np.asarray(R).reshape(-1)[0])), dev["ys"], dev["fms"], dev["fPs"], dev["sms"], dev["sPs"], dev["ll"])
 
     def run_fused():
+        fms, fPs = (None, None) if args.no_filtered else (dev["fms"], dev["fPs"])
         ctx.call("pgps_gp_dev_f64", c_long(n), c_int(2), c_double(lam), B._ptr(N1), B._ptr(N2), B._ptr(Pinf), B._ptr(Hh),
-                 c_double(0.1), dev["ts"], c_double(0.0), dev["ys"], dev["fms"], dev["fPs"], dev["sms"], dev["sPs"], dev["ll"])
+                 c_double(0.1), dev["ts"], c_double(0.0), dev["ys"], fms, fPs, dev["sms"], dev["sPs"], dev["ll"])
 
     has_waves = hasattr(ctx.lib, "pgps_resident_wave_stamps")
     print(f"library {B._LIB_PATH}, per-wave stamps: {'yes' if has_waves else 'no'}")
     ctx.set_resident(2)
-    for name, fn in (("array", run_array), ("fused", run_fused)):
+    forms = (("fused, no filtered outputs", run_fused),) if args.no_filtered else (("array", run_array), ("fused", run_fused))
+    for name, fn in forms:
         for _ in range(10):
             fn()
         ctx.synchronize()
