@@ -189,8 +189,8 @@ def test_rowcoop_standalone_pks_forced_small_d(row_family):
 
 @pytest.mark.parametrize("name", ["rbf8", "c5_qp_m52", "rbf13"])
 def test_fp32_series_at_large_d_run_through_fp64(name):
-    """fp32 arrays at 7 <= d <= 16: widened, run on the fp64 row-cooperative kernels, narrowed (csrc/pgps_core.hip
-    scan_f32_via_f64) -- pkf, pkfs, stand-alone pks and discretise, against the fp64 oracle at fp32 tolerance."""
+    """fp32 arrays at 7 <= d <= 16: widened, run on the fp64 row-cooperative kernels, narrowed (csrc/pgps_scan_api.hip
+    f32_run_wide, disc_dev) -- pkf, pkfs, stand-alone pks and discretise, against the fp64 oracle at fp32 tolerance."""
     from pssgp import _backend as B
     from pssgp.kalman.parallel import pkf, pkfs, pks
     sde = _kernels()[name]().get_sde()

@@ -1,5 +1,5 @@
 """Times pkfs (fp64, 2^18 steps, device-resident arrays) with the lane-chunk and the row-cooperative kernels at state
-dimensions 3..6 -- the measurement behind the automatic switch at d = 5 (csrc/pgps_core.hip dispatch_scan)."""
+dimensions 3..6 -- the measurement behind the automatic switch at d = 5 (csrc/pgps_scan_api.hip choose_family)."""
 import ctypes
 import os
 import sys
