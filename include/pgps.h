@@ -630,6 +630,29 @@ int pgps_series_gp_ll_grad_adj_f64(pgps_series* s, int d, double lam, const doub
 int pgps_gp_ll_grad_adj_dev_f64(pgps_ctx* ctx, long N, int d, double lam, const double* N1, const double* N2,
                                 const double* Pinf, const double* H, double R, const double* ts, double t0, const double* ys,
                                 double* out);
+/* The same at B hyper-parameter settings over one series in one set of launches: `models` (HOST memory) as
+ * pgps_gp_ll_batch_* takes it, B rows [lam | N1 | N2 | Pinf | H | R]; out (B, 1 + d d + 2 d + 1), row b what
+ * pgps_gp_ll_grad_adj_dev_f64 returns for model b.  One workgroup per model in ONE launch where the single call takes its
+ * one-launch form, four launches of (workgroups, models) grids otherwise; steps per lane are fixed once per call from (B, N)
+ * (pgps_set_chunk honoured) and the models run in groups that fit pgps_set_batch_scratch, so a row does not depend on its
+ * place in the table, on the other rows or on the groups.  The _dev form takes device pointers ts, ys, out, synchronises the
+ * stream once to copy the table in, and is asynchronous afterwards.  B or N < 1, a null pointer, lam <= 0 or R <= 0 in a
+ * row: PGPS_E_INVALID; d outside 1..3: PGPS_E_UNSUPPORTED_DIM; host forms: a non-finite ll in a row: PGPS_E_NUMERIC. */
+int pgps_gp_ll_grad_adj_batch_f64(pgps_ctx* ctx, int B, long N, int d, const double* models, const double* ts, double t0,
+                                  const double* ys, double* out);
+int pgps_gp_ll_grad_adj_batch_dev_f64(pgps_ctx* ctx, int B, long N, int d, const double* models, const double* ts, double t0,
+                                      const double* ys, double* out);
+int pgps_series_gp_ll_grad_adj_batch_f64(pgps_series* s, int B, int d, const double* models, double* out);
+/* ... and for B general LTI models on the row-cooperative kernels (fp64, 2 <= d <= 16; other d: PGPS_E_UNSUPPORTED_DIM):
+ * `models` (HOST memory) as pgps_lti_ll_batch_* takes it, B rows [F | Pinf | H | R]; out (B, 1 + d d + 2 d + 1), row b what
+ * pgps_lti_ll_grad_dev_f64 returns for model b.  The chain length is fixed once per call from (B, N) (pgps_set_chunk
+ * honoured); the models run in groups under the batch budget (default 1 GiB; about 2 N d d doubles per model).  Errors as
+ * above (R <= 0 in a row: PGPS_E_INVALID). */
+int pgps_lti_ll_grad_batch_f64(pgps_ctx* ctx, int B, long N, int d, const double* models, const double* ts, const double* ys,
+                               double t0, double* out);
+int pgps_lti_ll_grad_batch_dev_f64(pgps_ctx* ctx, int B, long N, int d, const double* models, const double* ts,
+                                   const double* ys, double t0, double* out);
+int pgps_series_lti_ll_grad_batch_f64(pgps_series* s, int B, int d, const double* models, double* out);
 /* ... and for ANY kernel's LTI model (F, Pinf, H: host pointers; fp64, 2 <= d <= PGPS_MAX_DIM): pgps_lti_ll_f64 /
  * pgps_lti_predict_f64 / pgps_lti_ll_batch_f64 (models: B rows [F | Pinf | H | R], d <= 16) on the resident series and its
  * merged query grid -- the evaluation loop of an optimiser or sampler over an RBF / Periodic / composite kernel. */

@@ -496,6 +496,59 @@ static int gp_predict_batch_host(pgps_ctx* ctx, int B, long N, long K, int d, co
 PGPS_DEFINE_PREDICT_BATCH(f64, double)
 PGPS_DEFINE_PREDICT_BATCH(f32, float)
 // ---------------------------------------------------------------------------------------------
+// batched log-likelihood and adjoints: B hyper-parameter settings over one series (fused path, d <= 3, fp64)
+// ---------------------------------------------------------------------------------------------
+// out (B, 1 + d d + 2 d + 1) on the device: row b = [ll | Abar | Ubar | Hbar | Rbar] of model b, as gp_adj_dev defines it
+int pgps::gp_adj_batch_dev(pgps_ctx* ctx, int B, long N, int d, const double* models_host, const double* ts, double t0,
+                           const double* ys, double* out) {
+    if (!ctx || B < 1 || N < 1 || !models_host || !ts || !ys || !out) return PGPS_E_INVALID;
+    if (d < 1 || d > 3) return PGPS_E_UNSUPPORTED_DIM;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::vector<double> packed;
+    TRY(gp_pack_models(B, d, models_host, packed));
+    double* dmodels;
+    TRY(stage_in<double>(ctx, ctx->st[0], nullptr, packed.size(), &dmodels));
+    // the packed vector dies with this frame: synchronous copy, as in gp_ll_batch_dev
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpy(dmodels, packed.data(), packed.size() * sizeof(double), hipMemcpyHostToDevice));
+    GpBatchArgs<double> b{};
+    b.N = N;
+    b.ts = ts;
+    b.ys = ys;
+    b.t_prev = t0;
+    b.models = dmodels;
+    RoctxRange range_("parallel_filter");
+    return for_dim<1, 3>(d, [&](auto D) { return launch_gp_adj_batch<double, D()>(ctx, B, b, out); });
+}
+
+// rows on the host: PGPS_E_NUMERIC when a row's log-likelihood is not finite
+int pgps::adj_batch_result(int B, int nout, const double* rows) {
+    for (int m = 0; m < B; ++m)
+        if (!std::isfinite(rows[(size_t)m * nout])) return PGPS_E_NUMERIC;
+    return PGPS_OK;
+}
+
+extern "C" int pgps_gp_ll_grad_adj_batch_dev_f64(pgps_ctx* ctx, int B, long N, int d, const double* models, const double* ts,
+                                                 double t0, const double* ys, double* out) {
+    return gp_adj_batch_dev(ctx, B, N, d, models, ts, t0, ys, out);
+}
+
+extern "C" int pgps_gp_ll_grad_adj_batch_f64(pgps_ctx* ctx, int B, long N, int d, const double* models, const double* ts,
+                                             double t0, const double* ys, double* out) {
+    if (!ctx || B < 1 || N < 1 || !models || !ts || !ys || !out) return PGPS_E_INVALID;
+    if (d < 1 || d > 3) return PGPS_E_UNSUPPORTED_DIM;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int nout = 1 + d * d + 2 * d + 1;
+    double *dts, *dys, *dout;
+    TRY(stage_in(ctx, ctx->st[10], ts, (size_t)N, &dts));
+    TRY(stage_in(ctx, ctx->st[4], ys, (size_t)N, &dys));
+    TRY(stage_in<double>(ctx, ctx->st[9], nullptr, (size_t)B * nout, &dout));
+    TRY(gp_adj_batch_dev(ctx, B, N, d, models, dts, t0, dys, dout));
+    TRY(stage_out(ctx, out, dout, (size_t)B * nout));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return adj_batch_result(B, nout, out);
+}
+// ---------------------------------------------------------------------------------------------
 // log-likelihood and its gradient (fused path, forward-mode duals through the scan)
 // ---------------------------------------------------------------------------------------------
 extern "C" int pgps_gp_ll_grad_dev_f64(pgps_ctx* ctx, long N, int d, int np, const double* model, const double* ts,

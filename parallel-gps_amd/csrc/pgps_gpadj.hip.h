@@ -21,10 +21,13 @@
 //                 (oracle/np_grad.py states the recursion); workgroup sums -> gpart.
 //   k_grad_lti_finalize (pgps_gradlti.h)  out = [ll | Abar (d^2) | Ubar (d) | Hbar (d) | Rbar], chunk partials in a fixed order.
 // A short series runs the three bodies in ONE launch of one workgroup (k_gp_gone), as k_gp_one does.
+// B models over one series (pgps_gp_ll_grad_adj_batch_*): k_gpb_gfwd / k_gpb_gback / k_gpb_gone at the end of this file, the
+// same bodies behind a per-model view; k_grad_lti_finalize_batch sums every model's partials.
 // fp64 only (the host contracts the adjoints with the model's derivatives: pssgp/_backend.py contract_grad_stats).
 #pragma once
 
 #include "pgps_fused.hip.h"
+#include "pgps_gradlti.h"
 
 namespace pgps {
 
@@ -324,6 +327,69 @@ __global__ __launch_bounds__(kBlock) void k_gp_gback(const GpAdjArgs ga) {
 // by the same CU behind a workgroup barrier)
 template <int D>
 __global__ __launch_bounds__(kBlock) void k_gp_gone(const GpAdjArgs ga) {
+    __shared__ GpLds<double, D> sh;
+    gp_reduce_body<double, D>(ga.g, sh.lds);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    gp_gfwd_body<D>(ga, sh);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    gp_gback_body<D>(ga, sh);
+    constexpr int NST = gp_adj_nstat<D>();
+    if (threadIdx.x == 0) {                     // (this lane wrote the partials)
+        ga.out[0] = ga.g.s.llpart[0];
+#pragma unroll
+        for (int i = 0; i < NST; ++i) ga.out[1 + i] = ga.gpart[i];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// batched adjoint pass (pgps_gp_ll_grad_adj_batch_*): G hyper-parameter settings over the same (ts, ys).  blockIdx.y selects
+// the model, as gp_batch_select does for the likelihood and the posterior; every model has its own slices of the filter
+// records, the adjoint records, the kept states, the workgroup partials and its own output row, so workgroups of different
+// models share nothing but the series.  Same bodies, same arithmetic as the single-model launches; the reduce launch is
+// k_gpb_reduce (pgps_fused.hip.h) on `b`.
+// ---------------------------------------------------------------------------------------------
+struct GpAdjBatchArgs {
+    GpBatchArgs<double> b;  // N, Lc, nblocks, nlanes, ts, ys, t_prev, models, spine, lpre, llpart, sspine, lsuf
+    double* xs;             // (G, bs_xs): kept states, ((d + sym) Lc, nlanes) per model
+    long bs_xs;
+    double* gpart;          // (G, nblocks, d^2 + 2 d + 1)
+    double* out;            // (G, 1 + d^2 + 2 d + 1)
+};
+
+template <int D>
+__device__ __forceinline__ GpAdjArgs gp_adj_batch_select(const GpAdjBatchArgs& ab) {
+    constexpr int NST = gp_adj_nstat<D>();
+    const long m = blockIdx.y;
+    GpAdjArgs ga{};
+    ga.g = gp_batch_select<double, D>(ab.b);
+    ga.g.s.sspine = ab.b.sspine + m * ab.b.nblocks * Dim<D>::NSMTH;
+    ga.g.s.lsuf = ab.b.lsuf + m * ab.b.nlanes * Dim<D>::NSMTH;
+    ga.xs = ab.xs + m * ab.bs_xs;
+    ga.gpart = ab.gpart + m * ab.b.nblocks * NST;
+    ga.out = ab.out + m * (1 + NST);
+    return ga;
+}
+
+template <int D>
+__global__ __launch_bounds__(kBlock) void k_gpb_gfwd(const GpAdjBatchArgs ab) {
+    const GpAdjArgs ga = gp_adj_batch_select<D>(ab);
+    __shared__ GpLds<double, D> sh;
+    gp_gfwd_body<D>(ga, sh);
+}
+
+template <int D>
+__global__ __launch_bounds__(kBlock) void k_gpb_gback(const GpAdjBatchArgs ab) {
+    const GpAdjArgs ga = gp_adj_batch_select<D>(ab);
+    __shared__ GpLds<double, D> sh;
+    gp_gback_body<D>(ga, sh);
+}
+
+// one workgroup per model, ONE launch (grid (1, G): blockIdx.x stays the workgroup's place in its model's series)
+template <int D>
+__global__ __launch_bounds__(kBlock) void k_gpb_gone(const GpAdjBatchArgs ab) {
+    const GpAdjArgs ga = gp_adj_batch_select<D>(ab);
     __shared__ GpLds<double, D> sh;
     gp_reduce_body<double, D>(ga.g, sh.lds);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -196,6 +196,8 @@ int lti_ll_batch_dev(pgps_ctx* ctx, int B, long N, int d, const double* models, 
                      double* ll);
 int lti_grad_dev(pgps_ctx* ctx, long N, int d, const double* F, const double* Pinf, const double* H, double R, const double* ts,
                  const double* ys, double t0, double* out);
+int lti_grad_batch_dev(pgps_ctx* ctx, int B, long N, int d, const double* models, const double* ts, const double* ys, double t0,
+                       double* out);
 int lti_predict_batch_merged(pgps_ctx* ctx, int B, size_t m, long K, int d, const double* models, const double* ts_m,
                              const double* ys_m, double t0, const int* qslot, double* mean, double* var, double* ll);
 
@@ -205,6 +207,11 @@ int gp_dev(pgps_ctx* ctx, long N, int d, double lam, const double* N1, const dou
            double R, const T* ts, double t0, const T* ys, T* fms, T* fPs, T* sms, T* sPs, double* ll);
 int gp_adj_dev(pgps_ctx* ctx, long N, int d, double lam, const double* N1, const double* N2, const double* Pinf, const double* H,
                double R, const double* ts, double t0, const double* ys, double* out);
+// ... of B models (host table of rows [lam | N1 | N2 | Pinf | H | R]) over one series: out (B, 1 + d d + 2 d + 1) [device]
+int gp_adj_batch_dev(pgps_ctx* ctx, int B, long N, int d, const double* models_host, const double* ts, double t0, const double* ys,
+                     double* out);
+// B result rows of nout doubles on the host: PGPS_E_NUMERIC when a row's log-likelihood (its first entry) is not finite
+int adj_batch_result(int B, int nout, const double* rows);
 template <typename T>
 int gp_predict_batch_merged(pgps_ctx* ctx, int B, size_t m, long K, int d, const double* models_host, const T* ts_m,
                             const T* ys_m, double t0, const int* qslot, T* mean, T* var, double* ll);

@@ -255,6 +255,27 @@ int launch_disc(pgps_ctx* ctx, long N, const T* F, const T* Pinf, const T* ts, T
 }
 
 // ---- fused-discretisation ("gp") launches: d <= 3 ------------------------------------------------------
+// The two geometry rules every fused launcher shares (one statement each: the batched calls promise results that do not
+// depend on how a batch is split, which holds only while they agree on the geometry).
+// One workgroup walks the whole series: steps per lane, rounded up to whole 4-step sub-tiles
+static inline long one_workgroup_steps(long N) {
+    const long v = (N + kBlock - 1) / kBlock;
+    return (v + 3) / 4 * 4;
+}
+// B models over one series of N steps, (workgroups, models) grids: pgps_set_chunk's value, else 16 steps per lane while the
+// batch keeps the chip covered (>= 1024 workgroups: the serial part is the efficient one), halved towards 4 when B x N is
+// small; a series shorter than four steps per lane of one workgroup takes one workgroup
+static inline int batch_steps_per_lane(const pgps_ctx* ctx, int B, long N) {
+    int lc = ctx->chunk;
+    if (lc <= 0) {
+        lc = 16;
+        while (lc > 4 && (long)B * ((N + (long)kBlock * lc - 1) / ((long)kBlock * lc)) < 1024) lc /= 2;
+        if (N < (long)kBlock * 4) lc = (int)((N + kBlock - 1) / kBlock);
+        if (lc < 1) lc = 1;
+    }
+    return lc;
+}
+
 template <typename T, int D, bool NT>
 static int launch_gp_nt(pgps_ctx* ctx, GpArgs<T> g, int want_filtered, int want_smoothed) {
     ScanArgs<T>& a = g.s;
@@ -288,9 +309,7 @@ int launch_gp(pgps_ctx* ctx, GpArgs<T> g, int want_filtered, int want_smoothed) 
         const bool one = ctx->one_launch != 0 && ctx->chunk <= 0 &&
                          a.N <= (ctx->one_launch > 0 ? (long)ctx->one_launch : (long)kOneLaunchAuto);
         if (one) {
-            long v = (a.N + kBlock - 1) / kBlock;
-            v = (v + 3) / 4 * 4;
-            a.Lc = (int)v;
+            a.Lc = (int)one_workgroup_steps(a.N);
             a.nblocks = 1;
         }
         a.nlanes = (long)a.nblocks * kBlock;
@@ -322,15 +341,7 @@ template <typename T, int D>
 int launch_gp_batch(pgps_ctx* ctx, int B, GpBatchArgs<T> b) {
     if constexpr (D <= 3) {
         HIPCHK(ctx, hipSetDevice(ctx->device));
-        // steps per lane: the serial part is the efficient one, so as long as the batch keeps the chip
-        // covered (>= 1024 workgroups) use 16 steps per lane; halve towards 4 when B x N is small
-        int lc = ctx->chunk;
-        if (lc <= 0) {
-            lc = 16;
-            while (lc > 4 && (long)B * ((b.N + (long)kBlock * lc - 1) / ((long)kBlock * lc)) < 1024) lc /= 2;
-            if (b.N < (long)kBlock * 4) lc = (int)((b.N + kBlock - 1) / kBlock);
-            if (lc < 1) lc = 1;
-        }
+        const int lc = batch_steps_per_lane(ctx, B, b.N);
         b.Lc = lc;
         b.nblocks = (int)((b.N + (long)kBlock * lc - 1) / ((long)kBlock * lc));
         b.nlanes = (long)b.nblocks * kBlock;
@@ -371,19 +382,11 @@ int launch_gp_predict_batch(pgps_ctx* ctx, int B, GpBatchArgs<T> b) {
         const bool one = ctx->batch_form == 1 && b.N <= kBatchOneMax;
         int lc;
         if (one) {
-            long v = (b.N + kBlock - 1) / kBlock;
-            v = (v + 3) / 4 * 4;
+            const long v = one_workgroup_steps(b.N);
             if (v > 0x7fffffffL) return PGPS_E_INVALID;
             lc = (int)v;
         } else {
-            // as launch_gp_batch: 16 steps per lane while the batch keeps the chip covered, halved towards 4 when B x N is small
-            lc = ctx->chunk;
-            if (lc <= 0) {
-                lc = 16;
-                while (lc > 4 && (long)B * ((b.N + (long)kBlock * lc - 1) / ((long)kBlock * lc)) < 1024) lc /= 2;
-                if (b.N < (long)kBlock * 4) lc = (int)((b.N + kBlock - 1) / kBlock);
-                if (lc < 1) lc = 1;
-            }
+            lc = batch_steps_per_lane(ctx, B, b.N);
         }
         b.Lc = lc;
         b.nblocks = one ? 1 : (int)((b.N + (long)kBlock * lc - 1) / ((long)kBlock * lc));
@@ -454,9 +457,7 @@ int launch_gp_adj(pgps_ctx* ctx, GpArgs<double> g, double* out) {
         const bool one = ctx->one_launch != 0 && ctx->chunk <= 0 &&
                          a.N <= (ctx->one_launch > 0 ? (long)ctx->one_launch : (long)kOneLaunchAuto);
         if (one) {
-            long v = (a.N + kBlock - 1) / kBlock;
-            v = (v + 3) / 4 * 4;
-            a.Lc = (int)v;
+            a.Lc = (int)one_workgroup_steps(a.N);
             a.nblocks = 1;
         }
         a.nlanes = (long)a.nblocks * kBlock;
@@ -491,6 +492,78 @@ int launch_gp_adj(pgps_ctx* ctx, GpArgs<double> g, double* out) {
     }
 }
 template int launch_gp_adj<PGPS_INST_T, PGPS_INST_D>(pgps_ctx*, GpArgs<double>, double*);
+
+// ---- the same for B models over one series (pgps_gp_ll_grad_adj_batch_*): out (B, 1 + d^2 + 2 d + 1) on the device -----
+template <typename T, int D>
+int launch_gp_adj_batch(pgps_ctx* ctx, int B, GpBatchArgs<double> b, double* out) {
+    if constexpr (D <= 3 && std::is_same<T, double>::value) {
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        // form and geometry are fixed HERE, once per call, from (B, N): a row then depends neither on its place in the table,
+        // nor on the other rows, nor on the group it runs in.  One workgroup per model where launch_gp_adj takes ONE launch
+        const bool one = ctx->one_launch != 0 && ctx->chunk <= 0 &&
+                         b.N <= (ctx->one_launch > 0 ? (long)ctx->one_launch : (long)kOneLaunchAuto);
+        int lc;
+        if (one) lc = (int)one_workgroup_steps(b.N);
+        else lc = batch_steps_per_lane(ctx, B, b.N);
+        b.Lc = lc;
+        b.nblocks = one ? 1 : (int)((b.N + (long)kBlock * lc - 1) / ((long)kBlock * lc));
+        b.nlanes = (long)b.nblocks * kBlock;
+        if (b.nblocks > 65535) return PGPS_E_INVALID;
+        constexpr int NX = D + Dim<D>::SYM, NST = gp_adj_nstat<D>();
+        // scratch of ONE model: the scan records in ctx->ws, the kept states and the workgroup partials in ctx->gadj
+        const size_t nb = (size_t)b.nblocks, nl = (size_t)b.nlanes;
+        auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+        const size_t s_xs = up((size_t)lc * NX * nl * sizeof(double));
+        const size_t per_ws = up(nb * Dim<D>::NFILT * 8) + up(nl * Dim<D>::NFILT * 8) + up(nb * Dim<D>::NSMTH * 8) +
+                              up(nl * Dim<D>::NSMTH * 8) + up(nb * 8);
+        const size_t per_gadj = s_xs + up(nb * NST * 8);
+        const size_t budget = ctx->batch_scratch ? ctx->batch_scratch : kBatchScratchDefault;
+        size_t group = budget / (per_ws + per_gadj);
+        if (group < 1) group = 1;                       // (one model is the least a launch can hold)
+        if (group > (size_t)B) group = (size_t)B;
+        if (group > 65535) group = 65535;               // grid.y
+        int rc = ensure(ctx, ctx->ws, group * per_ws);
+        if (rc) return rc;
+        rc = ensure(ctx, ctx->gadj, group * per_gadj);
+        if (rc) return rc;
+        // the slices of a kind lie side by side, strided by the unrounded record counts (gp_batch_select, gp_adj_batch_select)
+        char* base = (char*)ctx->ws.p;
+        size_t off = 0;
+        b.spine = (double*)(base + off);  off += up(group * nb * Dim<D>::NFILT * 8);
+        b.lpre = (double*)(base + off);   off += up(group * nl * Dim<D>::NFILT * 8);
+        b.sspine = (double*)(base + off); off += up(group * nb * Dim<D>::NSMTH * 8);
+        b.lsuf = (double*)(base + off);   off += up(group * nl * Dim<D>::NSMTH * 8);
+        b.llpart = (double*)(base + off);
+        GpAdjBatchArgs ab{};
+        ab.xs = (double*)ctx->gadj.p;
+        ab.bs_xs = (long)(s_xs / sizeof(double));
+        ab.gpart = ab.xs + group * (size_t)ab.bs_xs;
+        const double* models = b.models;
+        const dim3 block(kBlock);
+        for (size_t g0 = 0; g0 < (size_t)B; g0 += group) {
+            const unsigned G = (unsigned)((size_t)B - g0 < group ? (size_t)B - g0 : group);
+            b.models = models + g0 * kGpModelStride;
+            ab.b = b;
+            ab.out = out + g0 * (size_t)(1 + NST);
+            if (one) {
+                timed_launch(ctx, PGPS_K_FILTER_APPLY, k_gpb_gone<D>, dim3(1, G), block, 0, ab);
+            } else {
+                const dim3 grid(b.nblocks, G);
+                timed_launch(ctx, PGPS_K_FILTER_REDUCE, k_gpb_reduce<double, D>, grid, block, 0, b);
+                timed_launch(ctx, PGPS_K_FILTER_APPLY, k_gpb_gfwd<D>, grid, block, 0, ab);
+                timed_launch(ctx, PGPS_K_SMOOTHER_APPLY, k_gpb_gback<D>, grid, block, 0, ab);
+                timed_launch(ctx, PGPS_K_LL_FINALIZE, k_grad_lti_finalize_batch, dim3(1 + NST, G), dim3(256), 0, (long)b.nblocks, (int)NST,
+                             (const double*)b.llpart, (const double*)ab.gpart, ab.out);
+            }
+            HIPCHK(ctx, hipGetLastError());
+        }
+        return PGPS_OK;
+    } else {
+        (void)ctx; (void)B; (void)b; (void)out;
+        return PGPS_E_UNSUPPORTED_DIM;
+    }
+}
+template int launch_gp_adj_batch<PGPS_INST_T, PGPS_INST_D>(pgps_ctx*, int, GpBatchArgs<double>, double*);
 
 template int launch_gp_batch<PGPS_INST_T, PGPS_INST_D>(pgps_ctx*, int, GpBatchArgs<PGPS_INST_T>);
 template int launch_gp_predict_batch<PGPS_INST_T, PGPS_INST_D>(pgps_ctx*, int, GpBatchArgs<PGPS_INST_T>);

@@ -286,6 +286,11 @@ int launch_gp_batch(pgps_ctx* ctx, int B, GpBatchArgs<T> b);
 // context's batch budget
 template <typename T, int D>
 int launch_gp_predict_batch(pgps_ctx* ctx, int B, GpBatchArgs<T> b);
+// log-likelihood and the model's adjoints of B models over one series (pgps_gpadj.hip.h), fp64, d <= 3: b.N, b.ts, b.ys, b.t_prev,
+// b.models set by the caller; out (B, 1 + d^2 + 2 d + 1) [device].  Geometry once per call from (B, N); the models run in groups
+// that fit the context's batch budget (T names the unit that holds the instantiation: call it with T = double)
+template <typename T, int D>
+int launch_gp_adj_batch(pgps_ctx* ctx, int B, GpBatchArgs<double> b, double* out);
 // scratch budget of the batched fused predict when pgps_set_batch_scratch has not set one: the smallest budget beyond which
 // the measured time per model no longer improves (B = 1000, N + K = 5000, d = 2: 3.79, 2.83, 2.35, 2.19 ms at 8, 16, 32, 64 MiB,
 // 2.2 .. 2.7 ms at 256 MiB and 1 GiB)

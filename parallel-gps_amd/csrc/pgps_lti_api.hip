@@ -394,6 +394,39 @@ extern "C" int pgps_lti_ll_grad_f64(pgps_ctx* ctx, long N, int d, const double* 
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return std::isfinite(out[0]) ? PGPS_OK : PGPS_E_NUMERIC;
 }
+// ... of B models over one series on the row-cooperative kernels (2 <= d <= 16): models = B rows [F | Pinf | H | R] from host
+// memory, out (B, 1 + d d + 2 d + 1) on the device
+int pgps::lti_grad_batch_dev(pgps_ctx* ctx, int B, long N, int d, const double* models, const double* ts, const double* ys,
+                              double t0, double* out) {
+    if (!ctx || B < 1 || N < 1 || !models || !ts || !ys || !out) return PGPS_E_INVALID;
+    if (d < rc::kDimMin || d > rc::kDimMax) return PGPS_E_UNSUPPORTED_DIM;
+    const size_t dd = (size_t)d * d, ms = 2 * dd + d + 1;
+    for (int b = 0; b < B; ++b)
+        if (!(models[(size_t)b * ms + ms - 1] > 0.0)) return PGPS_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    double* table;
+    TRY(stage_in<double>(ctx, ctx->lti[0], models, (size_t)B * ms, &table));
+    return launch_ll_grad_lti_batch(ctx, N, d, B, table, (long)ms, ts, t0, ys, out);
+}
+extern "C" int pgps_lti_ll_grad_batch_dev_f64(pgps_ctx* c, int B, long N, int d, const double* models, const double* ts,
+                                              const double* ys, double t0, double* out) {
+    return lti_grad_batch_dev(c, B, N, d, models, ts, ys, t0, out);
+}
+extern "C" int pgps_lti_ll_grad_batch_f64(pgps_ctx* ctx, int B, long N, int d, const double* models, const double* ts,
+                                          const double* ys, double t0, double* out) {
+    if (!ctx || B < 1 || N < 1 || !models || !ts || !ys || !out) return PGPS_E_INVALID;
+    if (d < rc::kDimMin || d > rc::kDimMax) return PGPS_E_UNSUPPORTED_DIM;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int nout = 1 + grad_lti_nstat(d);
+    double *dts, *dys, *dout;
+    TRY(stage_in(ctx, ctx->st[10], ts, (size_t)N, &dts));
+    TRY(stage_in(ctx, ctx->st[4], ys, (size_t)N, &dys));
+    TRY(stage_in<double>(ctx, ctx->st[9], nullptr, (size_t)B * nout, &dout));
+    TRY(lti_grad_batch_dev(ctx, B, N, d, models, dts, dys, t0, dout));
+    TRY(stage_out(ctx, out, dout, (size_t)B * nout));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return adj_batch_result(B, nout, out);
+}
 extern "C" int pgps_lti_ll_f64(pgps_ctx* c, long N, int d, const double* F, const double* Pinf, const double* H, double R,
                                const double* ts, const double* ys, double t0, double* ll) {
     if (!ll) return PGPS_E_INVALID;

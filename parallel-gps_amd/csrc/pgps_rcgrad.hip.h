@@ -13,6 +13,32 @@
 namespace pgps {
 namespace rc {
 
+// Batched call (pgps_lti_ll_grad_batch_*): blockIdx.y selects one of a.batch models over the same ts, ys, as model_view
+// (pgps_rc.hip.h) does for the other row-cooperative kernels: the model's Pinf, H, R from its row [F | Pinf | H | R] of the
+// table and its own slices of the transition matrices, the kept moments, the scans' records and the partials.  The kernel
+// bodies below never see the difference; the single call (table == nullptr, strides 0, grid.y = 1) gets its arguments back.
+template <int D>
+__device__ __forceinline__ GradLtiArgs grad_model_view(const GradLtiArgs& a) {
+    GradLtiArgs b = a;
+    if (a.table) {
+        const long mb = blockIdx.y;
+        const double* row = a.table + mb * a.bs_model;
+        b.Pinf = row + D * D;
+        b.H = row + 2 * D * D;
+        b.R = row[2 * D * D + D];
+        b.Fs += mb * a.bs_F;
+        b.fPs += mb * a.bs_F;
+        b.fms += mb * a.bs_fm;
+        b.pre += mb * a.bs_pre;
+        b.sagg += mb * a.bs_sagg;
+        if (b.suf) b.suf += mb * a.bs_sagg;
+        b.llpart += mb * a.bs_ll;
+        b.gpart += mb * a.bs_gpart;
+        b.out += mb * a.bs_out;
+    }
+    return b;
+}
+
 // ====================================================================================================
 // forward: the Kalman pass of rc_apply1 (filter only, implicit process noise, filtered moments stored) with the adjoint
 // element of every step folded into the chain's total under the smoothing operator:
@@ -21,8 +47,9 @@ namespace rc {
 // Steps at or beyond N run as F = I, y missing: the identity element, state unchanged.
 // ====================================================================================================
 template <int D>
-__global__ __launch_bounds__(64) void rc_gapply1(const GradLtiArgs a) {
+__global__ __launch_bounds__(64) void rc_gapply1(const GradLtiArgs args) {
     using Real = double;
+    const GradLtiArgs a = grad_model_view<D>(args);
     __shared__ Real tl[4 * kPatch];
     const int lane = threadIdx.x & 15, row = threadIdx.x >> 4;
     Real* patch = patch_init(tl, row);
@@ -123,8 +150,9 @@ __global__ __launch_bounds__(64) void rc_gapply1(const GradLtiArgs a) {
 // Steps at or beyond N: F = I, y missing, dt = 0 -- nothing accumulates and (a, W) pass through.
 // ====================================================================================================
 template <int D>
-__global__ __launch_bounds__(64) void rc_gback1(const GradLtiArgs a) {
+__global__ __launch_bounds__(64) void rc_gback1(const GradLtiArgs args) {
     using Real = double;
+    const GradLtiArgs a = grad_model_view<D>(args);
     __shared__ Real tl[4 * kPatch];
     const int lane = threadIdx.x & 15, row = threadIdx.x >> 4;
     Real* patch = patch_init(tl, row);
@@ -238,11 +266,17 @@ __global__ __launch_bounds__(64) void rc_gback1(const GradLtiArgs a) {
 
 template <int D>
 int launch_rc_grad(pgps_ctx* ctx, const GradLtiArgs& a, int phase) {
-    const dim3 blk(64), g1((unsigned)((a.nchunk + 3) / 4));
+    const unsigned nb = a.batch > 1 ? (unsigned)a.batch : 1u;
+    const dim3 blk(64), g1((unsigned)((a.nchunk + 3) / 4), nb);
     switch (phase) {
         case 0: timed_launch(ctx, PGPS_K_FILTER_APPLY, rc_gapply1<D>, g1, blk, 0u, a); break;
         case 1: timed_launch(ctx, PGPS_K_SMOOTHER_APPLY, rc_gback1<D>, g1, blk, 0u, a); break;
         default:
+            if (a.table) {
+                hipLaunchKernelGGL(k_grad_lti_finalize_batch, dim3((unsigned)(1 + grad_lti_nstat(D)), nb), dim3(256), 0, ctx->stream,
+                                   (long)a.nchunk, grad_lti_nstat(D), (const double*)a.llpart, (const double*)a.gpart, a.out);
+                break;
+            }
             hipLaunchKernelGGL(k_grad_lti_finalize, dim3((unsigned)(1 + grad_lti_nstat(D))), dim3(256), 0, ctx->stream, (long)a.nchunk,
                                grad_lti_nstat(D), (const double*)a.llpart, (const double*)a.gpart, a.out);
             break;

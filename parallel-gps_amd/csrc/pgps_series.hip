@@ -161,6 +161,59 @@ extern "C" int pgps_series_gp_ll_grad_adj_f64(pgps_series* s, int d, double lam,
     return std::isfinite(out[0]) ? PGPS_OK : PGPS_E_NUMERIC;
 }
 
+// Where the B result rows of a batched gradient call on the resident series go: a small result straight into the pinned
+// buffer (grown if need be), as the single call's; else a staging buffer of the context
+static int series_rows_begin(pgps_series* s, size_t n, double** dout) {
+    pgps_ctx* ctx = s->ctx;
+    *dout = nullptr;
+    if (s->zero_copy && n * sizeof(double) <= ((size_t)8 << 20)) {
+        if (n > s->host_cap) {
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));     // (the buffer is replaced: nothing may still write it)
+            if (series_host(s, n + 64) != PGPS_OK && series_host(s, 2 * (size_t)s->K + 64) != PGPS_OK) return PGPS_E_NOMEM;
+        }
+        if (s->zero_copy && n <= s->host_cap) *dout = s->hdev;
+    }
+    if (!*dout) TRY(stage_in<double>(ctx, ctx->st[9], nullptr, n, dout));
+    return PGPS_OK;
+}
+static int series_rows_end(pgps_series* s, int B, int nout, const double* dout, double* out) {
+    pgps_ctx* ctx = s->ctx;
+    const size_t n = (size_t)B * nout;
+    if (dout != s->hdev) {
+        TRY(stage_out(ctx, out, dout, n));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    } else {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        std::memcpy(out, s->host, n * sizeof(double));
+    }
+    return adj_batch_result(B, nout, out);
+}
+
+// the same for B models (pgps_gp_ll_grad_adj_batch_f64) on the resident series: out (B, 1 + d d + 2 d + 1) on the host
+extern "C" int pgps_series_gp_ll_grad_adj_batch_f64(pgps_series* s, int B, int d, const double* models, double* out) {
+    if (!s || B < 1 || !models || !out) return PGPS_E_INVALID;
+    if (d < 1 || d > 3) return PGPS_E_UNSUPPORTED_DIM;
+    pgps_ctx* ctx = s->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int nout = 1 + d * d + 2 * d + 1;
+    double* dout;
+    TRY(series_rows_begin(s, (size_t)B * nout, &dout));
+    TRY(gp_adj_batch_dev(ctx, B, s->N, d, models, s->ts, s->t0, s->ys, dout));
+    return series_rows_end(s, B, nout, dout, out);
+}
+// ... and for B general LTI models [F | Pinf | H | R] of one state dimension 2 .. 16 (pgps_lti_ll_grad_batch_f64)
+extern "C" int pgps_series_lti_ll_grad_batch_f64(pgps_series* s, int B, int d, const double* models, double* out) {
+    if (!s || B < 1 || !models || !out) return PGPS_E_INVALID;
+    if (d < rc::kDimMin || d > rc::kDimMax) return PGPS_E_UNSUPPORTED_DIM;
+    pgps_ctx* ctx = s->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int nout = 1 + grad_lti_nstat(d);
+    double* dout;
+    TRY(series_rows_begin(s, (size_t)B * nout, &dout));
+    TRY(lti_grad_batch_dev(ctx, B, s->N, d, models, s->ts, s->ys, s->t0, dout));
+    return series_rows_end(s, B, nout, dout, out);
+}
+
 // predict_f at the query grid set by pgps_series_set_queries_f64: K means and variances (and the log-likelihood of the
 // training series: the query rows are missing observations and contribute nothing) on the host when the call returns
 extern "C" int pgps_series_gp_predict_f64(pgps_series* s, int d, double lam, const double* N1, const double* N2,

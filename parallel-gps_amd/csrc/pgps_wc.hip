@@ -2448,6 +2448,15 @@ int launch_disc_rc(pgps_ctx* ctx, long N, int d, const double* F, const double* 
 
 static inline size_t rc_align(size_t x) { return (x + 255) / 256 * 256; }
 
+// Steps per chain of the batched row-cooperative calls (log-likelihood, predict, gradient), B models over N steps: the
+// models multiply the chains, keep about 8192 in flight; at most 128 steps, at least 8.  One statement for all of them:
+// a row of a batch must not depend on which call, or which group of a call, it runs in.
+static inline long rc_batch_chain_steps(long N, int B) {
+    long lw = (N * (long)B + 8191) / 8192;
+    if (lw > 128) lw = 128;
+    return lw < 8 ? 8 : lw;
+}
+
 template <typename Real>
 static int scan_rc_entry(pgps_ctx* ctx, ScanArgs<Real> sa, int d, Mode mode, int store_f, const int* qslot, Real* pmean,
                          Real* pvar, int batch = 1, long bs_model = 0, int geom_batch = 0, long bs_out = 0);
@@ -2529,10 +2538,7 @@ static int scan_rc_entry(pgps_ctx* ctx, ScanArgs<Real> sa, int d, Mode mode, int
         long lw = (sa.N + 4095) / 4096;
         if (lw > cap) { lw = (sa.N + 8191) / 8192; if (lw < 128) lw = 128; }     // 8192 chains, two full rounds of blocks
         const int gb = geom_batch > batch ? geom_batch : batch;     // (a group of a larger call keeps the call's geometry)
-        if (gb > 1) {                           // the models multiply the chains: keep about 8192 in flight
-            lw = ((long)sa.N * gb + 8191) / 8192;
-            if (lw > 128) lw = 128;
-        }
+        if (gb > 1) lw = rc_batch_chain_steps(sa.N, gb);
         a.Lw = (int)(lw < 8 ? 8 : lw > 512 ? 512 : lw);
     }
     a.nchunk = (sa.N + a.Lw - 1) / a.Lw;
@@ -2664,6 +2670,90 @@ int launch_ll_grad_lti(pgps_ctx* ctx, long N, int d, const double* model, double
     g.suf = suf;
     if ((rcode = grad_level1_rc(ctx, d, g, 1))) return rcode;
     return grad_level1_rc(ctx, d, g, 2);
+}
+
+// ====================================================================================================
+// The same for B models over one series (pgps_lti_ll_grad_batch_*): the batched pieces of the log-likelihood and predict
+// batches -- discretisation with implicit process noise, rc_reduce1 behind model_view, the Kogge-Stone levels with their
+// batch stride -- and rc_gapply1 / rc_gback1 behind grad_model_view (pgps_rcgrad.hip.h), blockIdx.y = model.  The chain
+// length is fixed HERE from (B, N), and both scans run as the whole call's do whatever the group, so a row depends
+// neither on its place in the table, nor on the other rows, nor on the groups the budget cuts the table into.
+// ====================================================================================================
+constexpr size_t kGradBatchScratchDefault = (size_t)1 << 30;        // as the general-LTI predict batch (pgps_lti_api.hip)
+
+int launch_ll_grad_lti_batch(pgps_ctx* ctx, long N, int d, int B, const double* table, long bs_model, const double* ts, double t0,
+                             const double* ys, double* out) {
+    RoctxRange range_("parallel_filter");
+    if (!ctx || N < 1 || B < 1 || !table || bs_model < 1 || !ts || !ys || !out) return PGPS_E_INVALID;
+    if (d < rc::kDimMin || d > rc::kDimMax) return PGPS_E_UNSUPPORTED_DIM;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t dd = (size_t)d * d, n = (size_t)N;
+    int lw;
+    if (ctx->chunk > 0) {
+        lw = ctx->chunk > 4096 ? 4096 : ctx->chunk;
+    } else {
+        lw = (int)rc_batch_chain_steps(N, B);      // (B = 1 too: the batch entry point keeps one rule)
+    }
+    const long nchunk = (N + lw - 1) / lw;
+    const size_t nf = wc::nfilt(d), ns = wc::nsmth(d), nc = (size_t)nchunk, nst = (size_t)grad_lti_nstat(d);
+    // per model: Fs and the kept filtered covariances (N d^2 each), the kept means, the chains' records of both scans (two
+    // buffers each) and their partials
+    const size_t per_ws = rc_align(nc * nf * 8) * 2 + rc_align(nc * ns * 8) * 2 + rc_align(nc * 8) + rc_align(nc * nst * 8);
+    const size_t per_model = (2 * n * dd + n * d) * sizeof(double) + per_ws;
+    const size_t budget = ctx->batch_scratch ? ctx->batch_scratch : kGradBatchScratchDefault;
+    size_t group = budget / per_model;
+    if (group < 1) group = 1;                           // (one model is the least a launch can hold)
+    if (group > (size_t)B) group = (size_t)B;
+    if (group > 65535) group = 65535;                   // grid.y
+    int rcode;
+    if ((rcode = ensure(ctx, ctx->lti[4], group * n * dd * sizeof(double)))) return rcode;
+    if ((rcode = ensure(ctx, ctx->lti[6], group * n * dd * sizeof(double)))) return rcode;
+    if ((rcode = ensure(ctx, ctx->lti[7], group * n * d * sizeof(double)))) return rcode;
+    size_t off = 0;
+    const size_t o_aggA = off;  off = rc_align(off + group * nc * nf * sizeof(double));
+    const size_t o_aggB = off;  off = rc_align(off + group * nc * nf * sizeof(double));
+    const size_t o_sagA = off;  off = rc_align(off + group * nc * ns * sizeof(double));
+    const size_t o_sagB = off;  off = rc_align(off + group * nc * ns * sizeof(double));
+    const size_t o_ll = off;    off = rc_align(off + group * nc * sizeof(double));
+    const size_t o_gp = off;    off = rc_align(off + group * nc * nst * sizeof(double));
+    if ((rcode = ensure(ctx, ctx->ws, off))) return rcode;
+    char* base = (char*)ctx->ws.p;
+    double *aggA = (double*)(base + o_aggA), *aggB = (double*)(base + o_aggB);
+    double *sagA = (double*)(base + o_sagA), *sagB = (double*)(base + o_sagB);
+    double* Fs = (double*)ctx->lti[4].p;
+    for (size_t g0 = 0; g0 < (size_t)B; g0 += group) {
+        const int G = (int)((size_t)B - g0 < group ? (size_t)B - g0 : group);
+        const double* tab = table + g0 * (size_t)bs_model;
+        if ((rcode = launch_disc_rc(ctx, N, d, tab, tab + dd, ts, t0, Fs, nullptr, G, bs_model))) return rcode;     // implicit process noise
+        rc::RcArgsT<double> a{};
+        a.N = N; a.Lw = lw; a.nchunk = nchunk;
+        a.wfast = N >= 2 ? (N - 2) / (4L * lw) : 0;
+        a.P0 = tab + dd; a.H = tab + 2 * dd; a.R = 0.0; a.Fs = Fs; a.Qs = nullptr; a.ys = ys;
+        a.seg_first = 1; a.seg_last = 1; a.implicit_q = 1; a.store_f = 0;
+        a.batch = G; a.bs_F = (long)(n * dd); a.bs_agg = (long)(nc * nf); a.bs_model = bs_model;
+        a.Rs = tab + 2 * dd + d;                        // R of model b at tab[b * bs_model + 2 dd + d]
+        a.llpart = (double*)(base + o_ll);
+        a.agg1 = aggA;
+        if ((rcode = rc::level1(ctx, d, a, 0))) return rcode;
+        double* pre = aggA;
+        if ((rcode = rc::ks_scan(ctx, d, 0, nchunk, aggA, aggB, &pre, G, a.bs_agg, B))) return rcode;
+        GradLtiArgs g{};
+        g.N = N; g.d = d; g.Lw = lw; g.nchunk = nchunk;
+        g.Pinf = tab + dd; g.H = tab + 2 * dd; g.R = 0.0; g.Fs = Fs; g.ys = ys; g.ts = ts; g.t0 = t0;
+        g.fPs = (double*)ctx->lti[6].p; g.fms = (double*)ctx->lti[7].p;
+        g.pre = pre; g.sagg = sagA; g.llpart = a.llpart; g.gpart = (double*)(base + o_gp);
+        g.out = out + g0 * (1 + nst);
+        g.batch = G; g.table = tab; g.bs_model = bs_model;
+        g.bs_F = (long)(n * dd); g.bs_fm = (long)(n * d); g.bs_pre = (long)(nc * nf); g.bs_sagg = (long)(nc * ns);
+        g.bs_ll = nchunk; g.bs_gpart = (long)(nc * nst); g.bs_out = (long)(1 + nst);
+        if ((rcode = grad_level1_rc(ctx, d, g, 0))) return rcode;
+        double* suf = sagA;
+        if ((rcode = rc::ks_scan(ctx, d, 1, nchunk, sagA, sagB, &suf, G, g.bs_sagg, B))) return rcode;
+        g.suf = suf;
+        if ((rcode = grad_level1_rc(ctx, d, g, 1))) return rcode;
+        if ((rcode = grad_level1_rc(ctx, d, g, 2))) return rcode;
+    }
+    return PGPS_OK;
 }
 
 }  // namespace pgps

@@ -13,6 +13,7 @@ _LIB_PATH = os.environ.get("PGPS_LIB", os.path.join(_HERE, "libpgps.so"))
 
 PGPS_OK = 0
 E_UNSUPPORTED_DIM = -2
+E_NUMERIC = -5
 PGPS_K_NAMES = None
 COMM_ID_BYTES = 128             # PGPS_COMM_ID_BYTES
 
@@ -137,6 +138,13 @@ def _declare(lib):
         lib.pgps_mix_moments_dev_f64.argtypes = [P, c_int, c_long, P, P, P, P, P]
         lib.pgps_set_batch_scratch.argtypes = [P, ctypes.c_size_t]
         lib.pgps_set_batch_form.argtypes = [P, c_int]
+    if hasattr(lib, "pgps_gp_ll_grad_adj_batch_f64"):   # (absent from libraries built before log_likelihood_and_grad_batch)
+        for dev in ("", "_dev"):
+            getattr(lib, f"pgps_gp_ll_grad_adj_batch{dev}_f64").argtypes = [P, c_int, c_long, c_int, P, P, c_double, P, P]
+        lib.pgps_series_gp_ll_grad_adj_batch_f64.argtypes = [P, c_int, c_int, P, P]
+        for dev in ("", "_dev"):
+            getattr(lib, f"pgps_lti_ll_grad_batch{dev}_f64").argtypes = [P, c_int, c_long, c_int, P, P, P, c_double, P]
+        lib.pgps_series_lti_ll_grad_batch_f64.argtypes = [P, c_int, c_int, P, P]
     return lib
 
 
@@ -879,6 +887,38 @@ class LtiLlStream:
             ctx.close()
 
 
+class LtiGradStream(LtiLlStream):
+    """The same for the adjoint gradient (pgps_lti_ll_grad_dev_f64): one asynchronous evaluation per model of state dimension
+    d, rows [ll | Abar | Ubar | Hbar | Rbar] read once at the end -- the road of d = 17..32, which no batched kernel covers.
+    (Every evaluation's model is uploaded by a copy on the context's stream, so it is ordered behind the kernels of the
+    evaluation before it.)"""
+
+    def __init__(self, ts, ys, capacity, d, t0=0.0, device=0):
+        self.d, self.nout = int(d), 2 + int(d) * int(d) + 2 * int(d)
+        super().__init__(ts, ys, int(capacity) * self.nout, t0=t0, device=device)
+        self.rows = int(capacity)
+
+    def push(self, F, Pinf, H, R):
+        if self.count >= self.rows:
+            raise ValueError("LtiGradStream is full")
+        F, Pinf, H, d = _lti_model(F, Pinf, H)
+        if d != self.d:
+            raise ValueError("all models of a batch must have the same state dimension")
+        self.ctx.call("pgps_lti_ll_grad_dev_f64", c_long(self.n), c_int(d), _ptr(F), _ptr(Pinf), _ptr(H), c_double(float(R)),
+                      c_void_p(self.d_ts), c_void_p(self.d_ys), c_double(self.t0), c_void_p(self.d_ll + 8 * self.nout * self.count))
+        self.count += 1
+
+    def finish(self):
+        """The (count, 1 + d d + 2 d + 1) rows pushed so far (waits for the device); releases the device buffers."""
+        out = np.empty((self.count, self.nout), np.float64)
+        try:
+            if self.count:
+                self.ctx.d2h(out, self.d_ll)
+        finally:
+            self.close()
+        return out
+
+
 class _Packed(tuple):
     """(lam, N1, N2, Pinf, H, d) of Series.pack with the arrays' ctypes pointers made once (`.ptrs`: four data_as() calls are
     3 us of a 36 us evaluation)."""
@@ -1068,6 +1108,26 @@ class Series:
                                                                         float(R), self._goutp), "pgps_series_gp_ll_grad_adj_f64")
         return self._gout
 
+    def gp_ll_grad_adj_batch(self, models):
+        """B fused models in one set of launches (pgps_series_gp_ll_grad_adj_batch_f64): a (B, 1 + d d + 2 d + 1) array, row b
+        = [ll | Abar | Ubar | Hbar | Rbar] of model b.  `models` as gp_ll_batch takes them, or a table."""
+        packed, d = _gp_rows(models)
+        out = np.empty((packed.shape[0], 2 + d * d + 2 * d), np.float64)
+        with self.ctx.lock:
+            check(self.ctx, self.ctx.lib.pgps_series_gp_ll_grad_adj_batch_f64(self.handle, packed.shape[0], d, _ptr(packed), _ptr(out)),
+                  "pgps_series_gp_ll_grad_adj_batch_f64")
+        return out
+
+    def lti_ll_grad_batch(self, models):
+        """The same for B general LTI models [(F, Pinf, H, R)] of one state dimension 2 .. 16, or their table
+        (pgps_series_lti_ll_grad_batch_f64): the models side by side on the row-cooperative kernels."""
+        table, d = _lti_table(models)
+        out = np.empty((table.shape[0], 2 + d * d + 2 * d), np.float64)
+        with self.ctx.lock:
+            check(self.ctx, self.ctx.lib.pgps_series_lti_ll_grad_batch_f64(self.handle, table.shape[0], d, _ptr(table), _ptr(out)),
+                  "pgps_series_lti_ll_grad_batch_f64")
+        return out
+
     def gp_predict(self, packed, R):
         """(mean (K,), var (K,), ll) at the query grid of set_queries()."""
         lam, N1, N2, Pinf, H, d = packed
@@ -1119,6 +1179,12 @@ class Series:
 
 def _lti_table(models):
     """(B x [F | Pinf | H | R] float64 table, d) of a list of (F, Pinf, H, R), all of one state dimension."""
+    if isinstance(models, np.ndarray):          # already a table: 2 d^2 + d + 1 columns
+        cols = models.shape[1] if models.ndim == 2 else -1
+        d = next((k for k in range(LTI_DIM_MIN, LTI_BATCH_DIM_MAX + 1) if 2 * k * k + k + 1 == cols), None)
+        if d is None:
+            raise ValueError(f"a general-LTI model table has 2 d^2 + d + 1 columns (d = {LTI_DIM_MIN}..{LTI_BATCH_DIM_MAX}), got shape {models.shape}")
+        return np.ascontiguousarray(models, dtype=np.float64), d
     d, table = None, None
     for b, (F, Pinf, H, R) in enumerate(models):
         F, Pinf, H, dm = _lti_model(F, Pinf, H)
@@ -1185,6 +1251,52 @@ def gp_ll_batch(models, ts, ys, t0=0.0, device=0):
     out = np.zeros(len(models), np.float64)
     get_context(device).call(f"pgps_gp_ll_batch_{suf}", c_int(len(models)), c_long(ts_a.shape[0]), c_int(d), _ptr(packed),
                              _ptr(ts_a), c_double(float(t0)), _ptr(ys_a), _ptr(out))
+    return out
+
+
+def gp_ll_grad_adj_batch(models, ts, ys, t0=0.0, device=0):
+    """Log-likelihood and the model's adjoints of B fused (Matern-family, d <= 3) models over one float64 series in one set
+    of launches (pgps_gp_ll_grad_adj_batch_f64).  `models` as gp_ll_batch takes them, or a table.  Returns a
+    (B, 1 + d d + 2 d + 1) array, row b = [ll | Abar | Ubar | Hbar | Rbar] of model b (split_grad_stats)."""
+    ts_a = _prep(ts, np.float64, (-1,))
+    ys_a = _prep(ys, np.float64, (-1,))
+    if ys_a.shape[0] != ts_a.shape[0]:
+        raise ValueError(f"observations has {ys_a.shape[0]} rows, the series {ts_a.shape[0]} steps")
+    packed, d = _gp_rows(models)
+    ctx = get_context(device)
+    if not hasattr(ctx.lib, "pgps_gp_ll_grad_adj_batch_f64"):
+        raise RuntimeError("this libpgps has no pgps_gp_ll_grad_adj_batch_* entry points")
+    out = np.empty((packed.shape[0], 2 + d * d + 2 * d), np.float64)
+    ctx.call("pgps_gp_ll_grad_adj_batch_f64", c_int(packed.shape[0]), c_long(ts_a.shape[0]), c_int(d), _ptr(packed), _ptr(ts_a),
+             c_double(float(t0)), _ptr(ys_a), _ptr(out))
+    return out
+
+
+def lti_ll_grad_batch(models, ts, ys, t0=0.0, device=0):
+    """Log-likelihood and the model's adjoints of B general LTI models [(F, Pinf, H, R)] of one state dimension over one
+    series: a (B, 1 + d d + 2 d + 1) array, row b = [ll | Abar | Ubar | Hbar | Rbar] of model b (split_grad_stats).
+    d = 2 .. 16: one set of launches on the row-cooperative kernels (pgps_lti_ll_grad_batch_f64); d = 17 .. 32: one
+    asynchronous pgps_lti_ll_grad_dev_f64 per model on a private context, read once (LtiGradStream)."""
+    d = 0 if isinstance(models, np.ndarray) else np.asarray(models[0][0]).shape[0]
+    if LTI_BATCH_DIM_MAX < d <= LTI_DIM_MAX:
+        with LtiGradStream(ts, ys, len(models), d, t0=t0, device=device) as stream:
+            for F, Pinf, H, R in models:
+                stream.push(F, Pinf, H, R)
+            out = stream.finish()
+        if not np.all(np.isfinite(out[:, 0])):
+            raise PgpsError(E_NUMERIC, "pgps_lti_ll_grad_dev_f64: a log-likelihood of the batch is not finite")
+        return out
+    table, d = _lti_table(models)
+    ts_a = _prep(ts, np.float64, (-1,))
+    ys_a = _prep(ys, np.float64, (-1,))
+    if ys_a.shape[0] != ts_a.shape[0]:
+        raise ValueError(f"observations has {ys_a.shape[0]} rows, the series {ts_a.shape[0]} steps")
+    ctx = get_context(device)
+    if not hasattr(ctx.lib, "pgps_lti_ll_grad_batch_f64"):
+        raise RuntimeError("this libpgps has no pgps_lti_ll_grad_batch_* entry points")
+    out = np.empty((table.shape[0], 2 + d * d + 2 * d), np.float64)
+    ctx.call("pgps_lti_ll_grad_batch_f64", c_int(table.shape[0]), c_long(ts_a.shape[0]), c_int(d), _ptr(table), _ptr(ts_a),
+             _ptr(ys_a), c_double(float(t0)), _ptr(out))
     return out
 
 

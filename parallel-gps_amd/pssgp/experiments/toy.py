@@ -183,6 +183,123 @@ def hmc(gp, n_samples=1000, n_burnin=100, step_size=0.05, n_leapfrogs=10, seed=3
     return np.array(out), accepted / max(1, n_samples)
 
 
+# ---- C chains in lock step: one batched gradient call per leapfrog step for all of them ------------------------------
+def log_posterior_and_grad_batch(gp, U):
+    """log_posterior_and_grad at the C unconstrained points U (C, P) in ONE batched call
+    (StateSpaceGP.log_likelihood_and_grad_batch): (lp (C,), glp (C, P)).  The model's own parameters are left as they are.
+    If the batch as a whole fails (one row's likelihood is not finite, say), the rows are evaluated one by one and only
+    the failing ones read NaN."""
+    from .._backend import PgpsError
+    diverged = (PgpsError, ValueError, FloatingPointError)      # numeric divergence only: anything else is a bug and is raised
+    U = np.asarray(U, np.float64)
+    theta = _softplus(U)
+    try:
+        ll, g = gp.log_likelihood_and_grad_batch(theta)
+    except diverged:
+        ll, g = np.full(U.shape[0], np.nan), np.full(U.shape, np.nan)
+        for c in range(U.shape[0]):
+            try:
+                lc, gc = gp.log_likelihood_and_grad_batch(theta[c:c + 1])
+                ll[c], g[c] = lc[0], gc[0]
+            except diverged:                        # this row alone is divergent
+                pass
+    lp = np.asarray(ll, np.float64).copy()
+    glp = np.asarray(g, np.float64) / (1.0 + np.exp(-U))    # d softplus / du
+    for k, (mu, sd) in enumerate(PRIORS[:U.shape[1]]):
+        lp += -0.5 * ((U[:, k] - mu) / sd) ** 2 - math.log(sd) - 0.5 * math.log(2.0 * math.pi)
+        glp[:, k] += -(U[:, k] - mu) / sd ** 2
+    return lp, glp
+
+
+def hmc_chains_core(logp_and_grad_batch, U0, n_samples, n_burnin, step_sizes, n_leapfrogs, rngs, adapt=True):
+    """hmc() for C chains in lock step on a callable U (C, P) -> (lp (C,), g (C, P)): every leapfrog step of all chains
+    is ONE call.  Chain c draws from rngs[c] alone, has its own step size (adapted as hmc() adapts it) and accepts or
+    rejects alone; a chain whose proposal turns non-finite is given up for the rest of the trajectory (its row of the
+    later calls is its current point) and rejects.  A chain's arithmetic is elementwise in its own row, so its output
+    does not depend on the other chains as long as the callable's rows do not.  Returns (unconstrained samples
+    (C, n_samples, P), accepted proposals (C,), final points (C, P), final step sizes (C,))."""
+    U = np.array(U0, np.float64)
+    C, P = U.shape
+    eps = np.array(np.broadcast_to(np.asarray(step_sizes, np.float64), (C,)))
+    lp, g = logp_and_grad_batch(U)
+    lp, g = np.array(lp, np.float64), np.array(g, np.float64)
+    out = np.zeros((C, int(n_samples), P))
+    accepted = np.zeros(C, int)
+    L = int(n_leapfrogs)
+    for it in range(int(n_samples) + int(n_burnin)):
+        p0 = np.stack([rngs[c].standard_normal(P) for c in range(C)])
+        un, gn, lpn = U.copy(), g.copy(), lp.copy()
+        ok = np.ones(C, bool)
+        pn = p0 + 0.5 * eps[:, None] * gn
+        for l in range(L):
+            un = np.where(ok[:, None], un + eps[:, None] * pn, U)
+            lpe, ge = logp_and_grad_batch(un)
+            lpe, ge = np.asarray(lpe, np.float64), np.asarray(ge, np.float64)
+            fin = np.isfinite(lpe) & np.all(np.isfinite(ge), axis=1) & np.all(np.isfinite(un), axis=1)
+            live = ok & fin
+            lpn = np.where(live, lpe, lpn)
+            gn = np.where(live[:, None], ge, gn)
+            ok = live
+            if l + 1 < L:
+                pn = np.where(ok[:, None], pn + eps[:, None] * gn, pn)
+        pn = pn + 0.5 * eps[:, None] * gn
+        for c in range(C):
+            acc = False
+            if ok[c]:                               # (hmc() draws its uniform whenever the proposal is finite: so does this)
+                log_acc = (lpn[c] - 0.5 * (pn[c] @ pn[c])) - (lp[c] - 0.5 * (p0[c] @ p0[c]))
+                acc = bool(math.log(rngs[c].uniform()) < log_acc)
+            if acc:
+                U[c], lp[c], g[c] = un[c], lpn[c], gn[c]
+                if it >= n_burnin:
+                    accepted[c] += 1
+                elif adapt:
+                    eps[c] *= 1.05
+            elif adapt and it < n_burnin:
+                eps[c] *= 0.7
+        if it >= n_burnin:
+            out[:, it - int(n_burnin)] = U
+    return out, accepted, U, eps
+
+
+def hmc_chains(gp, n_chains, n_samples=1000, n_burnin=100, step_size=0.05, n_leapfrogs=10, seeds=None, u0=None, adapt=True):
+    """n_chains HMC chains over the unconstrained hyper-parameters in lock step: one batched gradient call
+    (log_posterior_and_grad_batch) per leapfrog step for all chains, so C chains cost about what one does where the
+    batched adjoint pass applies.  Chain c uses RandomState(seeds[c]) (default 31415 + c) and starts at u0[c] (default: the
+    model's current parameters for every chain); with the same seed, start and adapt=False it walks the path hmc() walks.
+    Returns constrained samples (C, n_samples, P) and the acceptance rates (C,); the model is left at chain 0's last point."""
+    C = int(n_chains)
+    seeds = [31415 + c for c in range(C)] if seeds is None else list(seeds)
+    if len(seeds) != C:
+        raise ValueError(f"{len(seeds)} seeds for {C} chains")
+    params = gp.trainable_parameters()
+    if u0 is None:
+        u = _softplus_inv(np.array([getattr(o, n) for o, n in params], np.float64))
+        U0 = np.tile(u, (C, 1))
+    else:
+        U0 = np.asarray(u0, np.float64).reshape(C, len(params))
+    rngs = [np.random.RandomState(s) for s in seeds]
+    out, accepted, U, _ = hmc_chains_core(lambda V: log_posterior_and_grad_batch(gp, V), U0, n_samples, n_burnin, step_size,
+                                          n_leapfrogs, rngs, adapt)
+    for (o, n), v in zip(params, _softplus(U[0])):
+        setattr(o, n, float(v))
+    return _softplus(out), accepted / max(1, int(n_samples))
+
+
+def split_rhat(samples):
+    """The split-R-hat of Gelman et al. (Bayesian Data Analysis, 3rd ed., section 11.4) per parameter: samples (C, n, P);
+    every chain is cut into its first and last floor(n / 2) draws, giving m = 2 C sequences of length h; with B / h the
+    variance of the sequence means and W the mean of the within-sequence variances (both with divisor - 1),
+    R-hat = sqrt(((h - 1) / h W + B / h) / W).  Returns (P,)."""
+    x = np.asarray(samples, np.float64)
+    if x.ndim != 3 or x.shape[1] < 4:
+        raise ValueError(f"samples must be (chains, draws >= 4, parameters), got {x.shape}")
+    h = x.shape[1] // 2
+    seq = np.concatenate([x[:, :h], x[:, x.shape[1] - h:]], axis=0)       # (2 C, h, P)
+    W = np.mean(np.var(seq, axis=1, ddof=1), axis=0)
+    B_over_h = np.var(np.mean(seq, axis=1), axis=0, ddof=1)
+    return np.sqrt(((h - 1.0) / h * W + B_over_h) / W)
+
+
 # ---- the reference's other two samplers (experiments/common.py:95-117 picks HMC, MALA or NUTS from tfp.mcmc) ---------
 def mala_chain(logp_and_grad, u0, n_samples, n_burnin, step_size, rng):
     """Metropolis-adjusted Langevin with tfp.mcmc's meaning of `step_size` (unit volatility): proposal

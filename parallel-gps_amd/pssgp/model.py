@@ -748,6 +748,57 @@ class StateSpaceGP:
             g = np.where(keep, g, 0.0)
         return config.default_float()(out[0]), g
 
+    def _adjoint_prepared(self):
+        """(F, Pinf, H, [(dF, dPinf, dH)]) of the kernel at its CURRENT setting for the adjoint pass of the general-LTI device
+        path, memoised by the setting; None when the kernel has no derivative rule, the model is not stationary or of a state
+        dimension the device path does not cover, or a derivative of the drift does not commute with it (the contraction
+        the device makes would not apply)."""
+        from . import _backend
+        from .kernels.sde_grads import sde_with_grads
+        key = self._param_key()
+        memo = getattr(self, "_grads_memo", None)
+        if memo is not None and memo[2] is self.kernel and memo[0] == key:
+            return memo[1]
+        prepared = None
+        scaled = self._rbf_scaled_sde()
+        if scaled is not None:
+            # a single RBF kernel near a setting whose SDE is built (the steps of an optimiser or sampler): the
+            # lengthscale is a scaling of time and the variance one of Pinf, so the model AND its derivatives are
+            # written down from the reference realisation -- no polynomial roots, balancing or Lyapunov solve per step
+            k = self.kernel
+            F = np.ascontiguousarray(scaled.F, np.float64)
+            P0 = np.ascontiguousarray(scaled.P0, np.float64)
+            H = np.ascontiguousarray(np.asarray(scaled.H, np.float64).reshape(-1))
+            zF, zP, zH = np.zeros_like(F), np.zeros_like(P0), np.zeros((1, H.size))
+            by_name = {"variance": (zF, P0 / float(k.variance), zH), "lengthscales": (-F / float(k.lengthscales), zP, zH)}
+            prepared = (F, P0, H, [by_name[a] for _, a in leaf_parameters(k)])
+            sde = None
+        else:
+            try:
+                sde, grads = sde_with_grads(self.kernel)
+            except (NotImplementedError, ZeroDivisionError, FloatingPointError):
+                sde = None
+        if sde is not None:
+            F, P0 = np.ascontiguousarray(sde.F, np.float64), np.ascontiguousarray(sde.P0, np.float64)
+            H = np.ascontiguousarray(np.asarray(sde.H, np.float64).reshape(-1))
+            L = np.asarray(sde.L, np.float64)
+            LQL = L @ np.atleast_2d(np.asarray(sde.Q, np.float64)) @ L.T
+            fmax = max(1.0, float(np.max(np.abs(F))))
+            ok = (_backend.LTI_DIM_MIN <= F.shape[0] <= _backend.LTI_DIM_MAX and np.all(np.isfinite(F)) and np.all(np.isfinite(P0))
+                  and np.max(np.abs(F @ P0 + P0 @ F.T + LQL)) <= 1e-8 * max(1.0, float(np.max(np.abs(LQL)))))
+            for dF, dP, dH in grads if ok else ():
+                if not np.all(np.isfinite(dP)):
+                    ok = False
+                if not dF.any():
+                    continue                    # (most parameters move Pinf or H only: nothing to commute)
+                if not np.all(np.isfinite(dF)) or \
+                        np.max(np.abs(F @ dF - dF @ F)) > 1e-9 * fmax * max(1.0, float(np.max(np.abs(dF)))):
+                    ok = False
+            if ok:
+                prepared = (F, P0, H, grads)
+        self._grads_memo = (key, prepared, self.kernel)
+        return prepared
+
     def _adjoint_ll_and_grad(self, wrt=None, prepared=None):
         """(ll, grad) by the adjoint pass of the general-LTI device path (pgps_lti_ll_grad_f64): the device returns the
         adjoints of the model (F, Pinf, H, R) from one filter pass and one reverse pass, pssgp.kernels.sde_grads the
@@ -755,52 +806,8 @@ class StateSpaceGP:
         None when the kernel has no derivative rule, a derivative of the drift does not commute with it (the contraction
         the device makes would not apply), or the library lacks the entry point."""
         from . import _backend
-        from .kernels.sde_grads import sde_with_grads
-        key = self._param_key()
-        memo = getattr(self, "_grads_memo", None)
-        if prepared is not None:
-            pass                                # the caller wrote the model and its derivatives down (Matern family)
-        elif memo is not None and memo[2] is self.kernel and memo[0] == key:
-            prepared = memo[1]
-        else:
-            prepared = None
-            scaled = self._rbf_scaled_sde()
-            if scaled is not None:
-                # a single RBF kernel near a setting whose SDE is built (the steps of an optimiser or sampler): the
-                # lengthscale is a scaling of time and the variance one of Pinf, so the model AND its derivatives are
-                # written down from the reference realisation -- no polynomial roots, balancing or Lyapunov solve per step
-                k = self.kernel
-                F = np.ascontiguousarray(scaled.F, np.float64)
-                P0 = np.ascontiguousarray(scaled.P0, np.float64)
-                H = np.ascontiguousarray(np.asarray(scaled.H, np.float64).reshape(-1))
-                zF, zP, zH = np.zeros_like(F), np.zeros_like(P0), np.zeros((1, H.size))
-                by_name = {"variance": (zF, P0 / float(k.variance), zH), "lengthscales": (-F / float(k.lengthscales), zP, zH)}
-                prepared = (F, P0, H, [by_name[a] for _, a in leaf_parameters(k)])
-                sde = None
-            else:
-                try:
-                    sde, grads = sde_with_grads(self.kernel)
-                except (NotImplementedError, ZeroDivisionError, FloatingPointError):
-                    sde = None
-            if sde is not None:
-                F, P0 = np.ascontiguousarray(sde.F, np.float64), np.ascontiguousarray(sde.P0, np.float64)
-                H = np.ascontiguousarray(np.asarray(sde.H, np.float64).reshape(-1))
-                L = np.asarray(sde.L, np.float64)
-                LQL = L @ np.atleast_2d(np.asarray(sde.Q, np.float64)) @ L.T
-                fmax = max(1.0, float(np.max(np.abs(F))))
-                ok = (_backend.LTI_DIM_MIN <= F.shape[0] <= _backend.LTI_DIM_MAX and np.all(np.isfinite(F)) and np.all(np.isfinite(P0))
-                      and np.max(np.abs(F @ P0 + P0 @ F.T + LQL)) <= 1e-8 * max(1.0, float(np.max(np.abs(LQL)))))
-                for dF, dP, dH in grads if ok else ():
-                    if not np.all(np.isfinite(dP)):
-                        ok = False
-                    if not dF.any():
-                        continue                    # (most parameters move Pinf or H only: nothing to commute)
-                    if not np.all(np.isfinite(dF)) or \
-                            np.max(np.abs(F @ dF - dF @ F)) > 1e-9 * fmax * max(1.0, float(np.max(np.abs(dF)))):
-                        ok = False
-                if ok:
-                    prepared = (F, P0, H, grads)
-            self._grads_memo = (key, prepared, self.kernel)
+        if prepared is None:                    # (else the caller wrote the model and its derivatives down: Matern family)
+            prepared = self._adjoint_prepared()
         if prepared is None:
             return None
         F, P0, H, grads = prepared
@@ -1269,6 +1276,134 @@ class StateSpaceGP:
             return _backend.lti_predict_stream(general, t, y, tq) + (None,)
         # no device form for this kernel (d = 1 outside the Matern family, d > 32): the loop over predict_f
         return self._predict_f_batch_loop(tq, thetas, params, True) + (None,)
+
+    # log_likelihood_and_grad_batch, single Matern kernel: settings from which the batched adjoint launches replace the loop of
+    # single gradient calls.  To be the smallest B at which the batch's median lies below the loop's minimum, as
+    # tools/grad_batch_bench.py reports it (`batch_from`); NOT MEASURED YET: 2 is the structural expectation -- a
+    # batched call is the launches of one gradient, the loop those of B
+    _GRAD_BATCH_FROM = 2
+
+    @staticmethod
+    def _matern_grad_contract(stats, table, names, lengthscales, variances):
+        """The host half of the batched adjoint gradient of a single Matern kernel, over the whole batch with array
+        operations: stats (B, 1 + d^2 + 2 d + 1) rows [ll | Abar | Ubar | Hbar | Rbar] of the device, table (B, 1 + 3 d^2 + d
+        + 1) rows [lam | N1 | N2 | Pinf | H | R] of _matern_table, names the parameters' attribute names in the order of the
+        gradient's columns.  The lengthscale scales time and the variance Pinf (as _fused_adjoint_ll_and_grad):
+            d ll / d l = -<Abar, F> / l with F = N1 - lam I,   d ll / d s2 = Ubar . (Pinf H^T) / s2,   d ll / d R = Rbar.
+        Returns grads (B, len(names))."""
+        stats, table = np.asarray(stats, np.float64), np.asarray(table, np.float64)
+        B = table.shape[0]
+        d = {6: 1, 16: 2, 32: 3}[table.shape[1]]
+        dd = d * d
+        F = table[:, 1:1 + dd].copy()
+        F[:, ::d + 1] -= table[:, :1]
+        Pinf = table[:, 1 + 2 * dd:1 + 3 * dd].reshape(B, d, d)
+        H = table[:, 1 + 3 * dd:1 + 3 * dd + d]
+        PH = np.einsum("bij,bj->bi", Pinf, H)
+        by_name = {"lengthscales": -np.sum(stats[:, 1:1 + dd] * F, axis=1) / np.asarray(lengthscales, np.float64),
+                   "variance": np.sum(stats[:, 1 + dd:1 + dd + d] * PH, axis=1) / np.asarray(variances, np.float64),
+                   "noise_variance": stats[:, 1 + dd + 2 * d]}
+        return np.stack([by_name[n] for n in names], axis=1)
+
+    # ... every other kernel (general-LTI models, d = 2 .. 32)
+    _GRAD_BATCH_FROM_LTI = 2
+
+    def _general_grad_batch(self, thetas, params, ser):
+        """The batched adjoint pass for kernels without the closed-form discretisation: every row's model and derivatives
+        from _adjoint_prepared() under assignment and restore (rows that differ in the noise only share one), ONE device
+        call for all rows (pgps_lti_ll_grad_batch_* at d <= 16, asynchronous single calls above), the contraction of
+        _backend.contract_grad_stats per row.  (stats (B, 1 + d d + 2 d + 1), grads (B, P)), or (None, None) where the loop
+        has to do it: the Matern family's own paths, a row without an adjoint rule, mixed state dimensions."""
+        from . import _backend
+        assert params[-1] == (self, "noise_variance")      # (the last column of thetas is R: the key below leaves it out)
+        fused, lti = self._device_forms()
+        if fused is not None or lti is None:
+            return None, None
+        rows, memo = [], {}
+        with self._parameters_restored(params):
+            for row in thetas:
+                for (o, n), v in zip(params, row):
+                    setattr(o, n, float(v))
+                key = tuple(float(v) for v in row[:-1])
+                if key not in memo:
+                    memo[key] = self._adjoint_prepared()
+                if memo[key] is None:
+                    return None, None
+                rows.append(memo[key])
+        d = rows[0][0].shape[0]
+        if any(r[0].shape[0] != d for r in rows):
+            return None, None
+        models = [(F, P0, H, float(R)) for (F, P0, H, _), R in zip(rows, thetas[:, -1])]
+        ts, Y = self.data
+        if ser is not None and d <= _backend.LTI_BATCH_DIM_MAX:
+            stats = ser.lti_ll_grad_batch(models)
+        else:
+            stats = _backend.lti_ll_grad_batch(models, ts.reshape(-1), Y.reshape(-1))
+        grads = np.stack([_backend.contract_grad_stats(_backend.split_grad_stats(stats[b], d), rows[b][2], rows[b][3])
+                          for b in range(len(rows))])
+        return stats, grads
+
+    def _ll_and_grad_batch_loop(self, thetas, params, wrt):
+        """log_likelihood_and_grad_batch as a loop: assign row b, log_likelihood_and_grad (its automatic, exact method)."""
+        B = thetas.shape[0]
+        lls, grads = np.zeros(B), np.zeros((B, len(params)))
+        with self._parameters_restored(params):
+            for b, row in enumerate(thetas):
+                for (o, n), v in zip(params, row):
+                    setattr(o, n, float(v))
+                lls[b], grads[b] = self.log_likelihood_and_grad(wrt=wrt)
+        return lls, grads
+
+    @_public_evaluation
+    def log_likelihood_and_grad_batch(self, thetas, wrt=None):
+        """(lls (B,), grads (B, P)): the marginal log-likelihood and its exact gradient at B hyper-parameter settings,
+        `thetas` (B, P) in the order of `trainable_parameters()`; row b is what log_likelihood_and_grad() returns with row b
+        assigned.  Columns not in `wrt` are 0.  The model's own parameters are untouched on every exit path.  parallel=True.
+
+        A single Matern-1/2, -3/2 or -5/2 kernel on a sorted float64 series from _GRAD_BATCH_FROM settings: ONE batched
+        adjoint pass on the device (pgps_gp_ll_grad_adj_batch_*: every setting's filter pass and reverse pass side by side,
+        on the resident series from the model's second evaluation), contracted over the batch by _matern_grad_contract.
+        Every other kernel with an adjoint rule (one state dimension 2 .. 32 for all rows) from _GRAD_BATCH_FROM_LTI
+        settings: _general_grad_batch (pgps_lti_ll_grad_batch_* up to d = 16, asynchronous single calls above).
+        Everything else -- float32 or unsorted series, a row without an adjoint rule, mixed state dimensions, smaller
+        batches, a library without the entry points -- is a loop over log_likelihood_and_grad; never differences unless
+        that method picks them itself.  A row that is not positive raises ValueError."""
+        if not self.parallel:
+            raise NotImplementedError("gradients run on the parallel (HIP) path: construct with parallel=True")
+        thetas, params = self._check_thetas(thetas)
+        B = thetas.shape[0]
+        ts, Y = self.data
+        if not np.all(thetas > 0.0):            # (variances, lengthscales, periods: a row that is not positive has no model)
+            bad = int(np.argmax(~np.all(thetas > 0.0, axis=1)))
+            raise ValueError(f"every hyper-parameter must be positive: row {bad} of thetas is {thetas[bad]}")
+        from . import _backend
+        # the series the batched entry points take: float64 and sorted -- resident from the model's second evaluation, the
+        # host arrays at its first
+        ser, host_ok = None, False
+        if ts.dtype == np.float64:
+            ser = self._device_series()
+            if ser is None and getattr(self, "_series", None) is not False:
+                t = ts.reshape(-1)
+                host_ok = bool(t.size >= 1 and np.all(np.diff(t) >= 0))
+        stats = grads = None
+        if ser is not None or host_ok:
+            lib = _backend.load_library()
+            table = self._matern_table(thetas, params) if B >= self._GRAD_BATCH_FROM else None
+            if table is not None and hasattr(lib, "pgps_gp_ll_grad_adj_batch_f64"):
+                stats = ser.gp_ll_grad_adj_batch(table) if ser is not None else \
+                    _backend.gp_ll_grad_adj_batch(table, ts.reshape(-1), Y.reshape(-1))
+                names = [n for _, n in params]
+                grads = self._matern_grad_contract(stats, table, names, thetas[:, names.index("lengthscales")],
+                                                   thetas[:, names.index("variance")])
+            elif table is None and B >= self._GRAD_BATCH_FROM_LTI and hasattr(lib, "pgps_lti_ll_grad_batch_f64"):
+                stats, grads = self._general_grad_batch(thetas, params, ser)
+        if stats is not None:
+            if wrt is not None:
+                keep = np.zeros(grads.shape[1], bool)
+                keep[[int(i) for i in wrt]] = True
+                grads = np.where(keep[None, :], grads, 0.0)
+            return stats[:, 0].astype(config.default_float()), grads
+        return self._ll_and_grad_batch_loop(thetas, params, wrt)
 
     def log_posterior_density(self):
         return self.maximum_log_likelihood_objective()
