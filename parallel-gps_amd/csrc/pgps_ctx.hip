@@ -69,8 +69,14 @@ extern "C" int pgps_create(int device, pgps_ctx** out) {
     if (hipDeviceGetAttribute(&ctx->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) ctx->n_cu = 0;
     if (const char* e = std::getenv("PGPS_WC_ROWS2")) ctx->wc_rows2 = std::atoi(e) & 15;            // diagnostic, see pgps_wc.hip
     if (const char* e = std::getenv("PGPS_WC_SERIAL3")) ctx->wc_serial3 = (e[0] == '1');      // diagnostic, see pgps_wc.hip
+    // (the resident launch's hand-off records are zeroed HERE and never again: a granule's tag is the epoch of the launch that
+    // wrote it, epochs only grow, so a zero or an old tag never matches)
     if (hipMalloc((void**)&ctx->status_word, pgps::kStatusBytes) != hipSuccess ||
-        hipMemset(ctx->status_word, 0, pgps::kStatusBytes) != hipSuccess) {
+        hipMemset(ctx->status_word, 0, pgps::kStatusBytes) != hipSuccess ||
+        hipMalloc((void**)&ctx->res_gran, pgps::kResGranBytes) != hipSuccess ||
+        hipMemset(ctx->res_gran, 0, pgps::kResGranBytes) != hipSuccess) {
+        if (ctx->res_gran) (void)hipFree(ctx->res_gran);
+        if (ctx->status_word) (void)hipFree(ctx->status_word);
         (void)hipStreamDestroy(ctx->own_stream);
         delete ctx;
         return PGPS_E_NOMEM;
@@ -93,6 +99,7 @@ extern "C" int pgps_destroy(pgps_ctx* ctx) {
     if (ctx->pin_h) (void)hipHostFree(ctx->pin_h);
     if (ctx->out_h) (void)hipHostFree(ctx->out_h);
     if (ctx->status_word) (void)hipFree(ctx->status_word);
+    if (ctx->res_gran) (void)hipFree(ctx->res_gran);
     for (auto& b : ctx->st)
         if (b.p) (void)hipFree(b.p);
     for (auto& b : ctx->lti)
@@ -473,11 +480,11 @@ bool resident_fits(const pgps_ctx* ctx, long N, int d, bool f32) {
     const bool own_chunk = ctx->resident > 0 && (ctx->chunk == 8 || ctx->chunk == 16);
     if ((ctx->chunk > 0 && !own_chunk) || ctx->block != 0 || ctx->stage_g >= 0 || ctx->single_pass > 0 || ctx->dma > 0) return false;
     if (ctx->family != 0 && ctx->family != 1) return false;
-    // one workgroup per CU, and at most kResMaxBlocks of them (the hand-off flags, one record per lane in the general fold)
+    // one workgroup per CU, and at most kResMaxBlocks of them (the hand-off records, one record per lane in the general fold)
     const long max_blocks = ctx->n_cu < kResMaxBlocks ? ctx->n_cu : kResMaxBlocks;
     if (N > (long)kBlock * (own_chunk ? ctx->chunk : kResLc) * max_blocks) return false;
     // not while the stream is being captured: the launch's barrier set and hand-off epoch are chosen per launch on the host,
-    // and a replayed graph would present the same ones again (counters already at their targets, flags already equal)
+    // and a replayed graph would present the same ones again (counters already at their targets, granule tags already equal)
     if (!(ctx->resident > 0 || N >= kResAutoMin)) return false;         // (before the query below: short series never pay for it)
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess) { (void)hipGetLastError(); return false; }

@@ -35,6 +35,7 @@ struct pgps_ctx {
     int shortcut = 1;                   // forgetting shortcut for the carry across workgroups (pgps_set_shortcut): 1 = where it applies, 0 = never
     int resident = -1;                  // one resident launch for filter + smoother (pgps_resident.hip.h): -1 = auto, 0 = off, 1 = on where it fits, 2 = on + phase stamps
     unsigned res_epoch = 0;             // launches of the resident kernel so far: picks the barrier's counter set
+    unsigned long long* res_gran = nullptr;     // the resident kernel's hand-off records (tagged granules, kResGranBytes): made and zeroed with the context
     DevBuf res_stamps;                  // diagnostics: (workgroups, 16) cycle stamps of the last resident launch
     int res_stamp_blocks = 0;
     int res_delay_tile = -1;            // diagnostics (pgps_debug_resident_delay): the workgroup that waits before it publishes, -1 = none
@@ -224,9 +225,9 @@ struct ResArgs {
     int* bar;               // this launch's barrier 1: 8 counter shards (32 ints apart) of first arrivals, zero on entry
     int* bar2;              // ... barrier 2: 8 shards of second arrivals (bar + kResBarSet / 2)
     int* bar_next;          // the next launch's set (both barriers): zeroed by this one
-    int* flags1;            // per workgroup: `epoch` once its filtering total is published (the neighbour hand-off)
-    int* flags2;            // ... once its smoothing total is (its log-likelihood partial follows, before its arrival at bar2)
-    int epoch;              // this launch's (never 0)
+    unsigned long long* gran1;      // per workgroup: its filtering total as tagged granules (the neighbour hand-off and the general fold)
+    unsigned long long* gran2;      // ... its smoothing total (its log-likelihood partial follows, before its arrival at bar2)
+    int epoch;              // this launch's (never 0): the tag of every granule it publishes
     long long* stamps;      // diagnostics (pgps_set_resident(ctx, 2)): (nblocks, 16) cycle stamps, else null
     // diagnostics (pgps_debug_resident_delay): start skew.  Workgroup `delay_tile` (-1: none) waits `delay_ticks` wall-clock
     // ticks before it publishes its phase-`delay_phase` total; wstamps (null unless armed) = the stamps buffer, whose slots
@@ -240,10 +241,14 @@ constexpr int kResLc = 16;                  // steps per lane: the chunk lives i
 constexpr int kStatusBytes = 8192;          // the context's status buffer: word 0 flags, 16.. tickets, 512.. the resident kernel's barrier counters
 constexpr int kResBarWord = 512;            // two sets (alternating launches) of two barriers x 8 shards x 32 ints (words 512 .. 1535)
 constexpr int kResBarSet = 2 * 8 * 32;
-constexpr int kResFlagWord = 1536;          // two arrays of 256 per-workgroup hand-off flags (words 1536 .. 2047)
-constexpr int kResMaxBlocks = 256;          // workgroups of one resident launch: the flag arrays, one record per lane in the general fold
-static_assert(kResBarWord + 2 * kResBarSet <= kResFlagWord, "barrier counters overlap the hand-off flags");
-static_assert((kResFlagWord + 2 * kResMaxBlocks) * 4 <= kStatusBytes, "hand-off flags outside the status buffer");
+constexpr int kResMaxBlocks = 256;          // workgroups of one resident launch: the hand-off records, one record per lane in the general fold
+static_assert((kResBarWord + 2 * kResBarSet) * 4 <= kStatusBytes, "barrier counters outside the status buffer");
+// A hand-off record: one 8-byte granule {low word: 32 bits of the total, high word: the launch's epoch} per 32-bit word of the
+// total, each written by ONE 8-byte store, the record padded to whole 128-byte lines.  The largest record (the filtering total
+// at d = 2 in fp64: 14 doubles = 28 granules) fits kResGranStride bytes; the context owns two arrays of kResMaxBlocks records
+// (filtering, smoothing totals), outside the growable workspace and zeroed once: no tag ever equals a later epoch.
+constexpr int kResGranStride = 256;
+constexpr size_t kResGranBytes = 2 * (size_t)kResMaxBlocks * kResGranStride;
 // does a whole-series filter + smoother call of N steps at dimension d (fp64 when !f32) take the resident launch?
 bool resident_fits(const pgps_ctx* ctx, long N, int d, bool f32);
 template <typename T, int D>

@@ -20,7 +20,7 @@ int launch_resident(pgps_ctx* ctx, ResArgs<T> ra, bool fused, bool smooth) {
     else if (a.N <= (long)kBlock * 8 * max_blocks) lc = 8;
     a.Lc = lc;
     a.nblocks = (int)((a.N + (long)kBlock * lc - 1) / ((long)kBlock * lc));
-    // every workgroup must be resident, and the hand-off flags and the general fold hold kResMaxBlocks workgroups
+    // every workgroup must be resident, and the hand-off records and the general fold hold kResMaxBlocks workgroups
     if (a.nblocks < 1 || a.nblocks > max_blocks) return PGPS_E_INVALID;
     a.nlanes = (long)a.nblocks * kBlock;
     a.seg_first = 1;
@@ -28,25 +28,24 @@ int launch_resident(pgps_ctx* ctx, ResArgs<T> ra, bool fused, bool smooth) {
     a.shortcut = ctx->shortcut != 0 ? 1 : 0;        // (a workgroup spans 2048 or 4096 steps; the test is on the data either way)
     auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t nb = (size_t)a.nblocks;
-    size_t off = 0;
-    const size_t o_spine = off;  off = up(off + nb * Dim<D>::NFILT * sizeof(T));
-    const size_t o_sspine = off; off = up(off + nb * Dim<D>::NSMTH * sizeof(T));
-    const size_t o_ll = off;     off = up(off + nb * sizeof(double));
+    // the workspace holds the log-likelihood partials alone: the totals travel as tagged granules in the context's own arrays
+    // (which never move or grow: a granule of an earlier launch keeps its tag, wherever the workspace has gone since)
+    const size_t off = up(nb * sizeof(double));
     int rc = ensure(ctx, ctx->ws, off);
     if (rc) return rc;
     ctx->ws_epoch++;
     char* base = (char*)ctx->ws.p;
-    a.spine = (T*)(base + o_spine);
-    a.sspine = (T*)(base + o_sspine);
-    a.llpart = (double*)(base + o_ll);
+    a.spine = nullptr;
+    a.sspine = nullptr;
+    a.llpart = (double*)base;
     a.status = ctx->status_word;
     const unsigned e = ctx->res_epoch++;
     ra.bar = ctx->status_word + kResBarWord + (e & 1u) * kResBarSet;
     ra.bar2 = ra.bar + kResBarSet / 2;
     ra.bar_next = ctx->status_word + kResBarWord + ((e + 1u) & 1u) * kResBarSet;
-    ra.flags1 = ctx->status_word + kResFlagWord;
-    ra.flags2 = ctx->status_word + kResFlagWord + kResMaxBlocks;
-    ra.epoch = (int)(e % 0x7ffffffeu) + 1;           // compared for equality: a stale flag of any earlier launch never matches
+    ra.gran1 = ctx->res_gran;
+    ra.gran2 = ctx->res_gran + (size_t)kResMaxBlocks * kResGranStride / sizeof(unsigned long long);
+    ra.epoch = (int)(e % 0x7ffffffeu) + 1;           // compared for equality: a stale granule of any earlier launch never matches
     ra.stamps = nullptr;
     ra.wstamps = nullptr;
     ra.delay_tile = -1;
@@ -61,9 +60,11 @@ int launch_resident(pgps_ctx* ctx, ResArgs<T> ra, bool fused, bool smooth) {
         ctx->res_stamp_blocks = a.nblocks;
     }
     if (skew) {
-        // every record a workgroup could read before it is published is NaN: a stale read cannot match by luck
+        // every record a workgroup could read before it is published is NaN: a stale read cannot match by luck (the granules'
+        // data words all ones, which is a NaN in either half of a double, under a tag of all ones, which is no epoch)
         HIPCHK(ctx, hipMemsetAsync(ctx->res_stamps.p, 0, nb * 16 * sizeof(long long), ctx->stream));
         HIPCHK(ctx, hipMemsetAsync(base, 0xFF, off, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(ctx->res_gran, 0xFF, kResGranBytes, ctx->stream));
         ra.wstamps = (long long*)ctx->res_stamps.p;
         ra.delay_tile = ctx->res_delay_tile;
         ra.delay_phase = ctx->res_delay_phase;

@@ -29,10 +29,14 @@
 // Q / filtered P / L / smoothed P in LDS: 528 B slots x 256 lanes = 132 KiB of the CU's 160, one workgroup per CU,
 // one wave per SIMD on 512 registers.
 //
-// Inter-workgroup visibility: the hand-off recipe of k_filter_single (pgps_kernels.hip.h; MI355X_MICROARCH.md, hand-offs
-// with sc1 loads in place of the acquire): one lane stores the record with agent-scope atomic (write-through) stores,
-// drains them, adds one arrival to the counter shard of its tile; eight lanes poll one shard each with relaxed
-// agent-scope loads; the records are read with agent-scope atomic loads only.  Every spin is bounded (status bit 1).
+// Inter-workgroup visibility.  A workgroup's total travels as TAGGED GRANULES (MI355X_MICROARCH.md, price list: handoff-1to1):
+// one naturally aligned 8-byte word {32 bits of the total, the launch's epoch} per 32-bit word of the total, each written by one
+// lane of the publishing wave in ONE agent-scope atomic (write-through) wave-store -- the data is its own flag: no drain in
+// front of a signal, no flag, no second load behind the poll.  The neighbour's lanes poll one granule each with relaxed
+// agent-scope loads until its tag is the epoch, and the poll that sees the tag holds the data.  The grid-wide barriers stay
+// as they were: the publishing wave drains its stores (s_waitcnt vmcnt(0)) behind the scan's tail, one lane adds an arrival to
+// the counter shard of its tile; eight lanes poll one shard each; records read behind a barrier are read with agent-scope
+// atomic loads only (the granules' data halves).  Every spin is bounded (status bit 1).
 // Each of the two barriers of a launch counts on eight shards of its OWN (target n each): a workgroup that runs ahead --
 // workgroup 0 never waits in phase 2, nor does one whose left neighbour's total has forgotten -- arrives at barrier 2
 // while others are still in phase 1, and on shared counters its second arrival could stand in for a first arrival that
@@ -67,7 +71,9 @@ struct ResCfg {
     static constexpr int SLOT = LC * MAT * W + 16;  // a lane's LDS slot (LC matrix records) + 16 B: conflict-free owner reads
     static constexpr int SLOTS = kWave * SLOT;      // per wave
     static constexpr int MST = GM::BYTES > 5120 ? GM::BYTES : 5120;     // per wave: staging of the means of one sub-tile / of 64 B per lane of y, t
-    static constexpr int NSCAN = kWaves * Dim<D>::NFILT * W;
+    static constexpr int NREC = Dim<D>::NFILT * W;                      // the largest record the scans and hand-offs pass through LDS
+    static constexpr int NSCAN = (kWaves + 1) * NREC;                   // the four wave totals of a scan, and one record handed over
+    static_assert(NSCAN % 8 == 0, "the log-likelihood sum's doubles follow the scan scratch");
     static constexpr int BYTES = kWaves * (SLOTS + MST) + NSCAN + kWaves * 8;
 };
 
@@ -227,7 +233,7 @@ __device__ __forceinline__ void res_drain_m(char* __restrict__ g /*wave-uniform*
 }
 
 // the wait for every workgroup's arrival at the grid-wide barrier whose counters `bar` holds (one arrival per workgroup).
-// The arriving lane has drained the stores it publishes (s_waitcnt vmcnt(0)) before it arrives.
+// The publishing wave has drained the stores it publishes (s_waitcnt vmcnt(0)) before one of its lanes arrives.
 __device__ __forceinline__ void res_wait_all(int* bar, int nblocks, int* status) {
     if (threadIdx.x < 8) {
         const int want = (nblocks - (int)threadIdx.x + 7) / 8;       // tiles whose index is threadIdx.x mod 8
@@ -239,22 +245,80 @@ __device__ __forceinline__ void res_arrive(int* bar, int tile) {
     __hip_atomic_fetch_add(bar + (tile & 7) * 32, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// The neighbour hand-off (round 5, with the forgetting shortcut): a workgroup that can take its carry from ONE neighbour's
-// total waits for that neighbour only -- a flag per workgroup, set to the launch's epoch by the lane that published the total
-// (after its stores have drained, like the arrival) -- and falls back to the grid-wide wait when the total has not forgotten
-// its past.  Every workgroup still ARRIVES at both barriers (the fallback and the log-likelihood sum count on it); nobody waits
-// for the slowest of 256 workgroups unless the data asks for it.  Waits go left in phase 2 and right in phase 3, each on a
-// flag set before its owner's own wait: no cycle.  Equality with the epoch: flags are never reset.
-__device__ __forceinline__ bool res_wait_epoch(const int* f, int want, int* status) {
-    int spins = 0;
-    while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != want) {
-        __builtin_amdgcn_s_sleep(2);
-        if (++spins > (1 << 22)) {
-            atomicOr(status, 2);
-            return false;
-        }
+// The neighbour hand-off (with the forgetting shortcut): a workgroup that can take its carry from ONE neighbour's total waits
+// for that neighbour's record only, and falls back to the grid-wide wait when the total has not forgotten its past.  Every
+// workgroup still ARRIVES at both barriers (the fallback and the log-likelihood sum count on it); nobody waits for the slowest
+// of 256 workgroups unless the data asks for it.  Waits go left in phase 2 and right in phase 3, each for a record published
+// before its owner's own wait: no cycle.
+//
+// The record is ResGran::NG granules {low word: data, high word: tag}; a granule is current when its tag EQUALS the launch's
+// epoch (the arrays are zeroed once, with the context; epochs start at 1 and only grow: tags are never reset).
+template <typename T, int N>
+struct ResGran {
+    static constexpr int WPS = (int)sizeof(T) / 4;      // 32-bit words per scalar
+    static constexpr int NG = N * WPS;                  // granules per record
+    static_assert(NG <= kWave && NG * 8 <= kResGranStride, "one wave-instruction and one place per record");
+};
+__device__ __forceinline__ unsigned long long* res_gran_rec(unsigned long long* g, int tile) {
+    return g + (long)tile * (kResGranStride / 8);
+}
+// Producer; called by the whole of wave 0, whose lane `holder` has the total in v[].  The holder hands it to its wave through
+// `hand` (LDS keeps a wave's accesses in order), lanes 0 .. NG - 1 store one granule each: ONE 8-byte wave-store.  Nothing
+// waits here: the wave drains behind the scan's tail, in front of its arrival.
+template <typename T, int N>
+__device__ __forceinline__ void res_publish(unsigned long long* rec, unsigned* hand, const T* v, int holder, int epoch) {
+    constexpr int NG = ResGran<T, N>::NG;
+    const int lane = threadIdx.x & (kWave - 1);
+    if (lane == holder) {
+        unsigned w[NG];
+        __builtin_memcpy(w, v, sizeof(w));
+#pragma unroll
+        for (int i = 0; i < NG; ++i) hand[i] = w[i];
     }
-    return true;
+    res_wave_sync();
+    if (lane < NG) {
+        const unsigned long long x = ((unsigned long long)(unsigned)epoch << 32) | hand[lane];
+        __hip_atomic_store(rec + lane, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// Consumer.  Lanes 0 .. NG - 1 of wave 0 poll one granule each; res_poll_first() puts the first load in flight (work may
+// follow it), res_take() re-reads the record until every polling lane has seen the epoch (the spin is bounded as every spin
+// of the launch is: a lane whose granule is still stale then raises status bit 1), passes the data words through `hand` and
+// leaves the record in every lane.
+template <typename T, int N>
+__device__ __forceinline__ unsigned long long res_poll_first(const unsigned long long* rec) {
+    if (threadIdx.x < ResGran<T, N>::NG) return __hip_atomic_load(rec + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return 0ull;
+}
+template <typename T, int N>
+__device__ __forceinline__ void res_take(const unsigned long long* rec, unsigned long long x, int epoch, unsigned* hand, int* status, T* v) {
+    constexpr int NG = ResGran<T, N>::NG;
+    if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) == 0) {        // wave 0: a scalar branch, and a scalar loop
+        const bool polls = threadIdx.x < NG;
+        bool stale = polls && (unsigned)(x >> 32) != (unsigned)epoch;
+        int spins = 0;
+        while (__builtin_amdgcn_ballot_w64(stale) != 0 && ++spins <= (1 << 22)) {
+            __builtin_amdgcn_s_sleep(2);
+            if (polls) x = __hip_atomic_load(rec + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            stale = polls && (unsigned)(x >> 32) != (unsigned)epoch;
+        }
+        if (stale) atomicOr(status, 2);
+        if (polls) hand[threadIdx.x] = (unsigned)x;
+    }
+    __syncthreads();
+    unsigned w[NG];
+#pragma unroll
+    for (int i = 0; i < NG; ++i) w[i] = hand[i];
+    __builtin_memcpy(v, w, sizeof(w));
+}
+// a record every granule of which is known to be out (its owner has arrived at the barrier this workgroup waited at)
+template <typename T, int N>
+__device__ __forceinline__ void res_load_record(const unsigned long long* rec, T* v) {
+    constexpr int NG = ResGran<T, N>::NG;
+    unsigned w[NG];
+#pragma unroll
+    for (int i = 0; i < NG; ++i) w[i] = (unsigned)__hip_atomic_load(rec + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __builtin_memcpy(v, w, sizeof(w));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -468,8 +532,9 @@ __device__ __forceinline__ void res_scan4(E& x, int lane) {
     }
 }
 // Exclusive workgroup scan.  The workgroup's total exists in ONE lane as soon as the cross-wave level is done -- lane 3
-// (FORWARD) / lane 0 of every wave -- and `publish(total)` runs there at once, in wave 0 (threadIdx.x 3 / 0): the
-// neighbour that waits for it no longer waits for the v_readlane broadcast, the final combine and the barrier below.
+// (FORWARD) / lane 0 of every wave -- and `publish(total)` runs at once, in the whole of wave 0 (the total is valid in its
+// lane 3 / 0: res_publish): the neighbour that waits for it does not wait for the v_readlane broadcast, the final combine
+// and the barrier below, under which the publishing wave's stores drain.
 template <typename E, bool FORWARD, typename PUB>
 __device__ __forceinline__ void res_block_scan_exclusive(const E& mine, E& excl, typename ElemTraits<E>::Scalar* lds, PUB&& publish) {
     using TR = ElemTraits<E>;
@@ -486,7 +551,7 @@ __device__ __forceinline__ void res_block_scan_exclusive(const E& mine, E& excl,
     TR::identity(t);
     if (lane < kWaves) rec_load(lds + lane * TR::N, t);
     res_scan4<E, FORWARD>(t, lane);
-    if (threadIdx.x == (FORWARD ? kWaves - 1 : 0)) publish(t);
+    if (wave == 0) publish(t);
     // (no branch on the wave's position: the first / last wave combines with the identity, which is exact)
     typename TR::Scalar pv[TR::N], iv[TR::N];
     {
@@ -580,6 +645,7 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
     char* slots = smem + wave * CFG::SLOTS;                                 // this wave's 64 slots
     char* mst = smem + kWaves * CFG::SLOTS + wave * CFG::MST;               // this wave's staging of the means
     T* lds = reinterpret_cast<T*>(smem + kWaves * (CFG::SLOTS + CFG::MST));   // the workgroup scans' scratch
+    unsigned* hand = reinterpret_cast<unsigned*>(smem + kWaves * (CFG::SLOTS + CFG::MST) + kWaves * CFG::NREC);     // one record handed over
     double* lds_ll = reinterpret_cast<double*>(smem + kWaves * (CFG::SLOTS + CFG::MST) + CFG::NSCAN);
     char* myslot = slots + lane * SLOT;
     T* myrec = reinterpret_cast<T*>(myslot);
@@ -714,18 +780,21 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
     PGPS_RSTAMP_WAVE(0);
     PGPS_RSTAMP(1);
     FE excl;
-    // the workgroup's total is published from inside the scan, by the lane that holds it first (threadIdx.x 3)
+    // the workgroup's total is published from inside the scan, by wave 0, the moment its lane 3 holds it
     res_block_scan_exclusive<FE, true>(agg, excl, lds, [&](const FE& total) {
         T v[NF];
         pack(total, v);
-        if constexpr (SKEW) res_skew(ra, tile, 1);
-#pragma unroll
-        for (int i = 0; i < NF; ++i) pub_store(a.spine + (long)tile * NF + i, v[i]);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        pub_store(ra.flags1 + tile, ra.epoch);
-        if constexpr (SKEW) res_wstamp(ra, tile, 10);
-        res_arrive(ra.bar, tile);
+        if constexpr (SKEW) { if (lane == kWaves - 1) res_skew(ra, tile, 1); }
+        res_publish<T, NF>(res_gran_rec(ra.gran1, tile), hand, v, kWaves - 1, ra.epoch);
     });
+    // the arrival: behind the scan's tail, under which the granule stores have drained
+    if (wave == 0) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (lane == 0) {
+            if constexpr (SKEW) res_wstamp(ra, tile, 10);
+            res_arrive(ra.bar, tile);
+        }
+    }
     PGPS_RSTAMP(2);
     // (the wait: below, where the carry is taken -- for the left neighbour alone when its total has forgotten its past)
 
@@ -737,15 +806,7 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
     for (int i = 0; i < D; ++i) s.m[i] = T(0);
 #pragma unroll
     for (int i = 0; i < SYM; ++i) s.P[i] = P0[i];
-    bool waited_all = false;
     if (tile > 0) {
-        if (a.shortcut != 0) {
-            if (threadIdx.x == 0) res_wait_epoch(ra.flags1 + tile - 1, ra.epoch, a.status);
-            __syncthreads();
-        } else {
-            res_wait_all(ra.bar, a.nblocks, a.status);
-            waited_all = true;
-        }
         // The forgetting shortcut.  The carry into this tile is the prefix T_0 (x) ... (x) T_{tile-1} applied to the prior; in
         // ANY bracketing its (b, C) are those of the last total whenever that total's A vanishes: out.b = A_2 w + b_2,
         // out.C = A_2 N A_2^T + C_2 (parallel.py:100-118).  A total over 4096 steps of a filter that forgets (|A| shrinks by a
@@ -755,30 +816,29 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
         // fp32: thirty orders below the unit round-off; a NaN fails the test), identical in every lane (they read the same
         // words); otherwise the general fold below runs.  Both roads give the same bits whenever the shortcut applies.
         FE nb;
-        {
+        bool forget = false;
+        if (a.shortcut != 0) {
+            const unsigned long long* rec = res_gran_rec(ra.gran1, tile - 1);
             T v[NF];
-#pragma unroll
-            for (int i = 0; i < NF; ++i) v[i] = pub_load(a.spine + (long)(tile - 1) * NF + i);
+            res_take<T, NF>(rec, res_poll_first<T, NF>(rec), ra.epoch, hand, a.status, v);
             unpack(v, nb);
-        }
-        T amax = T(0);
+            T amax = T(0);
 #pragma unroll
-        for (int i = 0; i < MAT; ++i) amax = fmax(amax, fabs(nb.A[i]));
-        const bool forget = a.shortcut != 0 && amax <= ResForget<T>::kA;
+            for (int i = 0; i < MAT; ++i) amax = fmax(amax, fabs(nb.A[i]));
+            forget = amax <= ResForget<T>::kA;
+        }
         if (__builtin_amdgcn_readfirstlane((int)forget)) {
 #pragma unroll
             for (int i = 0; i < D; ++i) s.m[i] = nb.b[i];
 #pragma unroll
             for (int i = 0; i < SYM; ++i) s.P[i] = nb.C[i];
         } else {
-            if (!waited_all) res_wait_all(ra.bar, a.nblocks, a.status);     // every total to the left is needed
+            res_wait_all(ra.bar, a.nblocks, a.status);      // every total to the left is needed
             FE mine, left;
             filt_identity(mine);
             if ((int)threadIdx.x < tile) {
                 T v[NF];
-                const T* rec = reinterpret_cast<const T*>(reinterpret_cast<const char*>(a.spine) + threadIdx.x * (unsigned)(NF * sizeof(T)));
-#pragma unroll
-                for (int i = 0; i < NF; ++i) v[i] = pub_load(rec + i);
+                res_load_record<T, NF>(res_gran_rec(ra.gran1, (int)threadIdx.x), v);
                 unpack(v, mine);
             }
             res_block_reduce_ordered(mine, left, lds);
@@ -964,23 +1024,24 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
     PGPS_RSTAMP_WAVE(1);
     PGPS_RSTAMP(5);
     SE sexcl;
-    // the smoothing total first, from inside the scan (threadIdx.x 0): the left neighbour waits for it alone
+    // the smoothing total first, from inside the scan (wave 0; its lane 0 holds it): the left neighbour waits for it alone
     res_block_scan_exclusive<SE, false>(sagg, sexcl, lds, [&](const SE& stotal) {
         T vv[NS];
         pack(stotal, vv);
-        if constexpr (SKEW) res_skew(ra, tile, 2);
-#pragma unroll
-        for (int i = 0; i < NS; ++i) pub_store(a.sspine + (long)tile * NS + i, vv[i]);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        pub_store(ra.flags2 + tile, ra.epoch);
+        if constexpr (SKEW) { if (lane == 0) res_skew(ra, tile, 2); }
+        res_publish<T, NS>(res_gran_rec(ra.gran2, tile), hand, vv, 0, ra.epoch);
     });
     PGPS_RSTAMP(6);
+    // the first poll of the right neighbour's record goes out in front of the log-likelihood work below
+    const bool take_right = tile + 1 < a.nblocks && a.shortcut != 0;
+    unsigned long long poll0 = 0ull;
+    if (take_right) poll0 = res_poll_first<T, NS>(res_gran_rec(ra.gran2, tile + 1));
     {
         // then the log-likelihood partial, which only workgroup 0 reads, at the very end: its fp64 log and workgroup sum
         // run while this workgroup would wait for its right neighbour anyway (same values, same order of summation).
-        // The arrival at barrier 2 comes after BOTH records -- the smoothing total above and the partial here -- are
-        // drained, by the lane that stored them: the general fold below and workgroup 0's final sum wait for every
-        // arrival and then read both kinds.
+        // The arrival at barrier 2 comes after BOTH records -- the smoothing total's granules above and the partial here,
+        // all stored by wave 0 -- are drained: the general fold below and workgroup 0's final sum wait for every arrival
+        // and then read both kinds.
         const double v = ll.value();
         const double t = block_sum_double(v, lds_ll);
         if (threadIdx.x == 0) {
@@ -998,44 +1059,35 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
     for (int i = 0; i < D; ++i) s.m[i] = T(0);
 #pragma unroll
     for (int i = 0; i < SYM; ++i) s.P[i] = T(0);
-    waited_all = false;
+    bool waited_all = false;
     if (tile + 1 < a.nblocks) {
-        if (a.shortcut != 0) {
-            if (threadIdx.x == 0) res_wait_epoch(ra.flags2 + tile + 1, ra.epoch, a.status);
-            __syncthreads();
-        } else {
-            res_wait_all(ra.bar2, a.nblocks, a.status);
-            waited_all = true;
-        }
         // the same shortcut backwards: a smoothing total whose E vanishes (the product of 4096 smoother gains) hands the tile
         // before it its own (g, L), whatever follows (parallel.py:176-184: E = E_a E_b, g = E_a g_b + g_a, L = E_a L_b E_a^T + L_a)
         SE nb;
-        {
+        bool forget = false;
+        if (take_right) {
             T v[NS];
-#pragma unroll
-            for (int i = 0; i < NS; ++i) v[i] = pub_load(a.sspine + (long)(tile + 1) * NS + i);
+            res_take<T, NS>(res_gran_rec(ra.gran2, tile + 1), poll0, ra.epoch, hand, a.status, v);
             unpack(v, nb);
-        }
-        T emax = T(0);
+            T emax = T(0);
 #pragma unroll
-        for (int i = 0; i < MAT; ++i) emax = fmax(emax, fabs(nb.E[i]));
-        const bool forget = a.shortcut != 0 && emax <= ResForget<T>::kA;
+            for (int i = 0; i < MAT; ++i) emax = fmax(emax, fabs(nb.E[i]));
+            forget = emax <= ResForget<T>::kA;
+        }
         if (__builtin_amdgcn_readfirstlane((int)forget)) {
 #pragma unroll
             for (int i = 0; i < D; ++i) s.m[i] = nb.g[i];
 #pragma unroll
             for (int i = 0; i < SYM; ++i) s.P[i] = nb.L[i];
         } else {
-            if (!waited_all) { res_wait_all(ra.bar2, a.nblocks, a.status); waited_all = true; }
+            res_wait_all(ra.bar2, a.nblocks, a.status);
+            waited_all = true;
             SE mine, right;
             smth_identity(mine);
             const int b = tile + 1 + (int)threadIdx.x;
             if (b < a.nblocks) {
                 T v[NS];
-                const T* rec = reinterpret_cast<const T*>(reinterpret_cast<const char*>(a.sspine + (long)(tile + 1) * NS) +
-                                                          threadIdx.x * (unsigned)(NS * sizeof(T)));
-#pragma unroll
-                for (int i = 0; i < NS; ++i) v[i] = pub_load(rec + i);
+                res_load_record<T, NS>(res_gran_rec(ra.gran2, b), v);
                 unpack(v, mine);
             }
             res_block_reduce_ordered(mine, right, lds);
