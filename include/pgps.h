@@ -684,6 +684,35 @@ int pgps_lti_ll_grad_dev_f64(pgps_ctx*, long N, int d, const double* F, const do
 int pgps_series_lti_ll_grad_f64(pgps_series* s, int d, const double* F, const double* Pinf, const double* H, double R,
                                 double* out);
 
+/* ---- several outputs on one clock (fused path, fp64, d <= 3) ---------------------------------------------------------
+ * ys (N, M) row-major: M independent GPs that share the kernel, the noise and the inputs (GPflow's Y (N, M) with
+ * num_latent_gps = M).  Covariances, gains and innovation variances do not depend on y, so ONE covariance pass serves the M
+ * columns: the scan runs on column-tiled elements (shared A, C, J plus a tile of (b, eta) pairs; csrc/pgps_multi.hip.h) and
+ * reads the times, merges and discretises once per tile instead of once per column.
+ *   ll    (M,)    log-likelihood of every column (NULL allowed in the predict calls)
+ *   mean  (K, M)  row-major posterior means at the sorted query times tq (merged as in pgps_gp_predict_*)
+ *   var   (K,)    posterior variance: the same for every column
+ * A row of ys is observed in all columns or missing (NaN) in all columns.  The host-array forms check that (a mixed row:
+ * PGPS_E_INVALID) and return PGPS_E_NUMERIC when some ll[j] is not finite; for the _dev forms (device pointers for ts, ys,
+ * tq, mean, var, ll; they return with the launches enqueued) it is a PRECONDITION: a step counts as missing when the first
+ * column of a tile is NaN, and a NaN in another column of an observed row makes that column's results (and its ll)
+ * non-finite and leaves the other columns untouched.  Column j equals pgps_gp_predict_* on column j up to rounding (another
+ * bracketing of the same scans); a column's result depends neither on the other columns' data nor on its position; repeated
+ * calls agree bit for bit (no floating-point atomics).  When the filtered means of all columns exceed the batch budget
+ * (pgps_set_batch_scratch) the column tiles run in rounds.  Errors: M, N, K < 1, a null pointer, R <= 0, lam <= 0,
+ * N + K >= 2^31: PGPS_E_INVALID; d outside 1..3: PGPS_E_UNSUPPORTED_DIM. */
+int pgps_gp_ll_multi_f64(pgps_ctx*, long N, int M, int d, double lam, const double* N1, const double* N2, const double* Pinf,
+                         const double* H, double R, const double* ts, const double* ys, double t0, double* ll);
+int pgps_gp_ll_multi_dev_f64(pgps_ctx*, long N, int M, int d, double lam, const double* N1, const double* N2,
+                             const double* Pinf, const double* H, double R, const double* ts, const double* ys, double t0,
+                             double* ll);
+int pgps_gp_predict_multi_f64(pgps_ctx*, long N, long K, int M, int d, double lam, const double* N1, const double* N2,
+                              const double* Pinf, const double* H, double R, const double* ts, const double* ys, double t0,
+                              const double* tq, double* mean, double* var, double* ll);
+int pgps_gp_predict_multi_dev_f64(pgps_ctx*, long N, long K, int M, int d, double lam, const double* N1, const double* N2,
+                                  const double* Pinf, const double* H, double R, const double* ts, const double* ys,
+                                  double t0, const double* tq, double* mean, double* var, double* ll);
+
 #ifdef __cplusplus
 }
 #endif

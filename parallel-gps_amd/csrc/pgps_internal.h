@@ -303,6 +303,36 @@ constexpr size_t kBatchScratchDefault = 64u << 20;
 // form 1 of the batched fused predict (one workgroup per model, pgps_set_batch_form(ctx, 1)) is taken up to this many merged steps
 constexpr long kBatchOneMax = 65536;
 
+// M observation columns on one clock (pgps_multi.hip.h, pgps_multi_inst.hip): fp64, d <= 3.  One launch covers the column
+// groups [c_base, c_base + MC * gridDim.y); every group has its own slices of the scan scratch and of fms
+struct GpMultiArgs {
+    long N;                     // steps (merged steps in a predict call)
+    int M;                      // columns of ys, of pmean, entries of ll
+    int c_base;                 // first column of this launch
+    int Lc, nblocks;
+    long nlanes;
+    GpModel<double> m;          // the model and the (merged) times
+    double R;
+    const double* ys;           // (rows, M) row-major, NaN = missing: a row is missing in all columns or in none
+    const double* rows;         // (N,) the row of ys a step reads, as a double; NaN at a query step.  nullptr: step k reads row k
+    const int* qslot;           // (N,) slot of a query step in pmean / pvar, -1 at the training steps (predict only)
+    int ys_aligned, mean_aligned;       // ys / pmean start on a 16-byte boundary
+    double* spine;              // (groups, nblocks, NFILT_M)
+    double* lpre;               // (groups, NFILT_M, nlanes)
+    double* sspine;             // (groups, nblocks, NSMTH_M)
+    double* lsuf;               // (groups, NSMTH_M, nlanes)
+    double* llpart;             // (M, nblocks): all columns of the call
+    double* fms;                // (N, ldm, d) filtered means of this launch's columns
+    double* fPs;                // (N, d (d + 1) / 2) filtered covariances, packed upper triangles: written once per launch
+    int ldm;                    // columns of fms = MC * groups of a launch
+    double* pmean;              // (K, M)
+    double* pvar;               // (K,)
+};
+// ll (M,) [device] or null; predict != 0: a.rows, a.qslot, a.pmean, a.pvar set.  Picks the geometry once per call from
+// (M, N), carves the scratch and runs the column groups in rounds that fit the context's batch budget
+template <int D>
+int launch_gp_multi(pgps_ctx* ctx, GpMultiArgs a, int predict, double* ll);
+
 // merge of two sorted time arrays on the device + NaN marking of the query rows (pgps_core.hip)
 template <typename T>
 int launch_merge(pgps_ctx* ctx, long N, long K, const T* ts, const T* ys, const T* tq, T* ts_m, T* ys_m, int* qslot);

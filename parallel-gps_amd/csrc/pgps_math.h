@@ -1130,4 +1130,413 @@ PGPS_HD void smth_extend_last_u(SmthElem<T, D>& a) {
     for (int i = 0; i < D * D; ++i) a.E[i] = T(0);
 }
 
+// ------------------------------------------------------------------------------------
+// Column-tiled ("multi right-hand-side") forms: MC observation columns that share the model, the noise and the time grid.
+// A, C, J of a filtering element -- and E, L of a smoothing element, and every covariance -- do not depend on y, so one
+// copy serves the MC columns; only (b, eta), g and the means are per column.  Each function below does the matrix work of
+// its single-column namesake ONCE, in the same order of operations (the shared parts come out bit-identical to the
+// single-column functions'), and then applies it to the MC vector pairs.  `obs` says whether the step is observed: a step
+// is missing for all columns or for none (the caller tests one column); a NaN in another column of an observed step
+// poisons that column alone, because the columns share no arithmetic.  Scalar arithmetic only (the fp64 kernels of
+// pgps_multi.hip.h and the host build of tests/cpu_math).
+// ------------------------------------------------------------------------------------
+template <typename T, int D, int MC>
+struct FiltElemM {
+    T A[D * D];
+    T C[Dim<D>::SYM];
+    T J[Dim<D>::SYM];
+    T b[MC][D];
+    T eta[MC][D];
+    static constexpr int N = D * D + 2 * Dim<D>::SYM + 2 * MC * D;
+};
+template <typename T, int D, int MC>
+struct SmthElemM {
+    T E[D * D];
+    T L[Dim<D>::SYM];
+    T g[MC][D];
+    static constexpr int N = D * D + Dim<D>::SYM + MC * D;
+};
+template <typename T, int D, int MC>
+struct MeanCovM {
+    T P[Dim<D>::SYM];
+    T m[MC][D];
+};
+
+template <typename T, int D, int MC>
+PGPS_HD void filt_identity_m(FiltElemM<T, D, MC>& e) {
+#pragma unroll
+    for (int i = 0; i < D * D; ++i) e.A[i] = T(0);
+#pragma unroll
+    for (int i = 0; i < D; ++i) e.A[i * D + i] = T(1);
+#pragma unroll
+    for (int i = 0; i < Dim<D>::SYM; ++i) { e.C[i] = T(0); e.J[i] = T(0); }
+#pragma unroll
+    for (int c = 0; c < MC; ++c)
+#pragma unroll
+        for (int i = 0; i < D; ++i) { e.b[c][i] = T(0); e.eta[c][i] = T(0); }
+}
+
+// filt_first for MC columns
+template <typename T, int D, int MC>
+PGPS_HD void filt_first_m(FiltElemM<T, D, MC>& e, const T* P0 /*sym*/, const T* y /*MC*/, bool obs, const T* h, T R) {
+#pragma unroll
+    for (int i = 0; i < D * D; ++i) e.A[i] = T(0);
+#pragma unroll
+    for (int i = 0; i < Dim<D>::SYM; ++i) { e.C[i] = P0[i]; e.J[i] = T(0); }
+#pragma unroll
+    for (int c = 0; c < MC; ++c)
+#pragma unroll
+        for (int i = 0; i < D; ++i) { e.b[c][i] = T(0); e.eta[c][i] = T(0); }
+    if (obs) {
+        T u[D];
+        sym_vec<T, D>(P0, h, u);
+        const T S = dot_add<T, D>(h, u, R);
+        const T inv = recip(S);
+#pragma unroll
+        for (int c = 0; c < MC; ++c)
+#pragma unroll
+            for (int i = 0; i < D; ++i) e.b[c][i] = u[i] * (y[c] * inv);
+        sym_outer<T, D, true>(e.C, u, inv, e.C);
+    }
+}
+
+// filt_extend for MC columns: one predict of (A, C), one gain, MC residuals
+template <typename T, int D, int MC>
+PGPS_HD void filt_extend_m(FiltElemM<T, D, MC>& e, const T* F, const T* Q /*sym*/, const T* y /*MC*/, bool obs, const T* h, T R) {
+    T Ap[D * D], FC[D * D], Cp[Dim<D>::SYM], bp[MC][D];
+    mat_mul<T, D>(F, e.A, Ap);
+#pragma unroll
+    for (int c = 0; c < MC; ++c) mat_vec<T, D>(F, e.b[c], bp[c]);
+    predict_cov<T, D>(F, e.C, Q, FC, Cp);
+    if (!obs) {
+#pragma unroll
+        for (int i = 0; i < D * D; ++i) e.A[i] = Ap[i];
+#pragma unroll
+        for (int c = 0; c < MC; ++c)
+#pragma unroll
+            for (int i = 0; i < D; ++i) e.b[c][i] = bp[c][i];
+#pragma unroll
+        for (int i = 0; i < Dim<D>::SYM; ++i) e.C[i] = Cp[i];
+        return;
+    }
+    T u[D], v[D];
+    sym_vec<T, D>(Cp, h, u);
+    mat_t_vec<T, D>(Ap, h, v);
+    const T S = dot_add<T, D>(h, u, R);
+    const T inv = recip(S);
+#pragma unroll
+    for (int c = 0; c < MC; ++c) {
+        const T hb = dot_add<T, D>(h, bp[c], T(0));
+        const T res = y[c] - hb;
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            e.b[c][i] = bp[c][i] + (u[i] * inv) * res;
+            e.eta[c][i] += v[i] * (res * inv);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        const T Ki = u[i] * inv;
+#pragma unroll
+        for (int j = 0; j < D; ++j) e.A[i * D + j] = Ap[i * D + j] - Ki * v[j];
+    }
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = i; j < D; ++j) {
+            e.C[symi<D>(i, j)] = Cp[symi<D>(i, j)] - u[i] * u[j] * inv;
+            e.J[symi<D>(i, j)] += v[i] * v[j] * inv;
+        }
+}
+
+// M = I + C1 J2 (as filt_system forms it)
+template <typename T, int D>
+PGPS_HD void filt_system_mat(const T* C1, const T* J2, T* M) {
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            T acc = (i == j) ? T(1) : T(0);
+#pragma unroll
+            for (int k = 0; k < D; ++k) acc += C1[symi<D>(i, k)] * J2[symi<D>(k, j)];
+            M[i * D + j] = acc;
+        }
+}
+// w = b1 + C1 eta2 (as filt_system forms it)
+template <typename T, int D>
+PGPS_HD void filt_system_vec(const T* C1, const T* b1, const T* eta2, T* w) {
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        T wi = b1[i];
+#pragma unroll
+        for (int j = 0; j < D; ++j) wi += C1[symi<D>(i, j)] * eta2[j];
+        w[i] = wi;
+    }
+}
+
+// filt_combine for MC columns: ONE elimination of M = I + C1 J2 with 2 D + MC right-hand sides
+template <typename T, int D, int MC>
+PGPS_HD void filt_combine_m(const FiltElemM<T, D, MC>& e1, const FiltElemM<T, D, MC>& e2, FiltElemM<T, D, MC>& out) {
+    constexpr int NR = 2 * D + MC;
+    T M[D * D], B[D * NR], w[D];
+    filt_system_mat<T, D>(e1.C, e2.J, M);
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            B[i * NR + j] = e1.A[i * D + j];
+            B[i * NR + D + j] = e1.C[symi<D>(i, j)];
+        }
+#pragma unroll
+    for (int c = 0; c < MC; ++c) {
+        filt_system_vec<T, D>(e1.C, e1.b[c], e2.eta[c], w);
+#pragma unroll
+        for (int i = 0; i < D; ++i) B[i * NR + 2 * D + c] = w[i];
+    }
+    gj_solve<T, D, NR, true>(M, B);
+    T G[D * D], Nm[D * D], X[D * D];
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) { G[i * D + j] = B[i * NR + j]; Nm[i * D + j] = B[i * NR + D + j]; }
+    mat_mul<T, D>(e2.A, G, out.A);
+    mat_mul<T, D>(e2.A, Nm, X);
+    mat_mul_t_sym<T, D>(X, e2.A, e2.C, out.C);
+#pragma unroll
+    for (int c = 0; c < MC; ++c) {
+        T z[D], Jb[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) w[i] = B[i * NR + 2 * D + c];
+        mat_vec<T, D>(e2.A, w, out.b[c]);
+#pragma unroll
+        for (int i = 0; i < D; ++i) out.b[c][i] += e2.b[c][i];
+        sym_vec<T, D>(e2.J, e1.b[c], Jb);
+#pragma unroll
+        for (int i = 0; i < D; ++i) z[i] = e2.eta[c][i] - Jb[i];
+        mat_t_vec<T, D>(G, z, out.eta[c]);
+#pragma unroll
+        for (int i = 0; i < D; ++i) out.eta[c][i] += e1.eta[c][i];
+    }
+    sym_mul_mat<T, D>(e2.J, e1.A, X);
+    mat_t_mul_sym<T, D>(G, X, e1.J, out.J);
+}
+
+// filt_apply for MC columns
+template <typename T, int D, int MC>
+PGPS_HD void filt_apply_m(MeanCovM<T, D, MC>& s, const FiltElemM<T, D, MC>& e2) {
+    constexpr int NR = D + MC;
+    T M[D * D], B[D * NR], w[D];
+    filt_system_mat<T, D>(s.P, e2.J, M);
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) B[i * NR + j] = s.P[symi<D>(i, j)];
+#pragma unroll
+    for (int c = 0; c < MC; ++c) {
+        filt_system_vec<T, D>(s.P, s.m[c], e2.eta[c], w);
+#pragma unroll
+        for (int i = 0; i < D; ++i) B[i * NR + D + c] = w[i];
+    }
+    gj_solve<T, D, NR, true>(M, B);
+    T Nm[D * D], X[D * D];
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) Nm[i * D + j] = B[i * NR + j];
+#pragma unroll
+    for (int c = 0; c < MC; ++c) {
+#pragma unroll
+        for (int i = 0; i < D; ++i) w[i] = B[i * NR + D + c];
+        mat_vec<T, D>(e2.A, w, s.m[c]);
+#pragma unroll
+        for (int i = 0; i < D; ++i) s.m[c][i] += e2.b[c][i];
+    }
+    mat_mul<T, D>(e2.A, Nm, X);
+    mat_mul_t_sym<T, D>(X, e2.A, e2.C, s.P);
+}
+
+// Log-likelihoods of MC columns: log S_k is shared (LogLik's mantissa product and exponent count), the quadratic terms are
+// per column
+template <int MC>
+struct LogLikM {
+    double quad[MC];
+    double mant = 1.0;
+    long long expo = 0;
+    long long count = 0;
+    PGPS_HD LogLikM() {
+#pragma unroll
+        for (int c = 0; c < MC; ++c) quad[c] = 0.0;
+    }
+    PGPS_HD void add(const double* r /*MC*/, double S) {
+        const double rs = recip(S);
+#pragma unroll
+        for (int c = 0; c < MC; ++c) quad[c] += r[c] * r[c] * rs;
+        int e;
+        mant = std::frexp(mant * S, &e);
+        expo += e;
+        count += 1;
+    }
+    PGPS_HD double value(int c) const {
+        const double logdet = std::log(mant) + double(expo) * 0.6931471805599453;
+        return -0.5 * (double(count) * 1.8378770664093453 + logdet + quad[c]);
+    }
+};
+
+// kf_step for MC columns: mp (MC, D), Pp, FP are handed out for the smoothing element
+template <typename T, int D, int MC>
+PGPS_HD void kf_step_m(MeanCovM<T, D, MC>& s, const T* F, const T* Q /*sym*/, const T* y /*MC*/, bool obs, const T* h, T R,
+                       bool first, LogLikM<MC>& ll, T (*mp)[D], T* Pp, T* FP) {
+#pragma unroll
+    for (int c = 0; c < MC; ++c) mat_vec<T, D>(F, s.m[c], mp[c]);
+    predict_cov<T, D>(F, s.P, Q, FP, Pp);
+    T u[D];
+    sym_vec<T, D>(Pp, h, u);
+    const T S = dot_add<T, D>(h, u, R);
+    T mu[MC];
+#pragma unroll
+    for (int c = 0; c < MC; ++c) mu[c] = dot_add<T, D>(h, mp[c], T(0));
+    if (obs) {
+        double r[MC];
+#pragma unroll
+        for (int c = 0; c < MC; ++c) r[c] = ll_diff(y[c], mu[c]);
+        ll.add(r, ll_wide(S));
+    }
+    if (first) {
+        T u0[D];
+        sym_vec<T, D>(s.P, h, u0);
+        const T S0 = dot_add<T, D>(h, u0, R);
+        if (obs) {
+            const T inv = recip(S0);
+#pragma unroll
+            for (int c = 0; c < MC; ++c) {
+                const T res = y[c] - dot_add<T, D>(h, s.m[c], T(0));
+#pragma unroll
+                for (int i = 0; i < D; ++i) s.m[c][i] += u0[i] * (res * inv);
+            }
+            sym_outer<T, D, true>(s.P, u0, inv, s.P);
+        }
+        return;
+    }
+    if (obs) {
+        const T inv = recip(S);
+#pragma unroll
+        for (int c = 0; c < MC; ++c) {
+            const T res = y[c] - mu[c];
+#pragma unroll
+            for (int i = 0; i < D; ++i) s.m[c][i] = mp[c][i] + u[i] * (res * inv);
+        }
+        sym_outer<T, D, true>(Pp, u, inv, s.P);
+    } else {
+#pragma unroll
+        for (int c = 0; c < MC; ++c)
+#pragma unroll
+            for (int i = 0; i < D; ++i) s.m[c][i] = mp[c][i];
+#pragma unroll
+        for (int i = 0; i < Dim<D>::SYM; ++i) s.P[i] = Pp[i];
+    }
+}
+
+template <typename T, int D, int MC>
+PGPS_HD void smth_identity_m(SmthElemM<T, D, MC>& e) {
+#pragma unroll
+    for (int i = 0; i < D * D; ++i) e.E[i] = T(0);
+#pragma unroll
+    for (int i = 0; i < D; ++i) e.E[i * D + i] = T(1);
+#pragma unroll
+    for (int i = 0; i < Dim<D>::SYM; ++i) e.L[i] = T(0);
+#pragma unroll
+    for (int c = 0; c < MC; ++c)
+#pragma unroll
+        for (int i = 0; i < D; ++i) e.g[c][i] = T(0);
+}
+
+// smth_element for MC columns: one gain, one L
+template <typename T, int D, int MC>
+PGPS_HD void smth_element_m(const MeanCovM<T, D, MC>& s, const T (*mp)[D], const T* Pp, const T* FP, SmthElemM<T, D, MC>& e) {
+    smth_gain<T, D>(FP, Pp, e.E);
+#pragma unroll
+    for (int c = 0; c < MC; ++c) {
+        T Em[D];
+        mat_vec<T, D>(e.E, mp[c], Em);
+#pragma unroll
+        for (int i = 0; i < D; ++i) e.g[c][i] = s.m[c][i] - Em[i];
+    }
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = i; j < D; ++j) {
+            T acc = T(0);
+#pragma unroll
+            for (int k = 0; k < D; ++k)
+                acc += e.E[i * D + k] * FP[k * D + j] + e.E[j * D + k] * FP[k * D + i];
+            e.L[symi<D>(i, j)] = s.P[symi<D>(i, j)] - T(0.5) * acc;
+        }
+}
+
+template <typename T, int D, int MC>
+PGPS_HD void smth_last_m(const MeanCovM<T, D, MC>& s, SmthElemM<T, D, MC>& e) {
+#pragma unroll
+    for (int i = 0; i < D * D; ++i) e.E[i] = T(0);
+#pragma unroll
+    for (int i = 0; i < Dim<D>::SYM; ++i) e.L[i] = s.P[i];
+#pragma unroll
+    for (int c = 0; c < MC; ++c)
+#pragma unroll
+        for (int i = 0; i < D; ++i) e.g[c][i] = s.m[c][i];
+}
+
+// smth_combine for MC columns (a = earlier, b = later)
+template <typename T, int D, int MC>
+PGPS_HD void smth_combine_m(const SmthElemM<T, D, MC>& a, const SmthElemM<T, D, MC>& b, SmthElemM<T, D, MC>& out) {
+    T X[D * D];
+    mat_mul<T, D>(a.E, b.E, out.E);
+#pragma unroll
+    for (int c = 0; c < MC; ++c) {
+        T gv[D];
+        mat_vec<T, D>(a.E, b.g[c], gv);
+#pragma unroll
+        for (int i = 0; i < D; ++i) out.g[c][i] = gv[i] + a.g[c][i];
+    }
+    mat_mul_sym<T, D>(a.E, b.L, X);
+    mat_mul_t_sym<T, D>(X, a.E, a.L, out.L);
+}
+
+// smth_apply for MC columns
+template <typename T, int D, int MC>
+PGPS_HD void smth_apply_m(const SmthElemM<T, D, MC>& a, MeanCovM<T, D, MC>& s) {
+    T X[D * D], Ls[Dim<D>::SYM];
+#pragma unroll
+    for (int c = 0; c < MC; ++c) {
+        T gv[D];
+        mat_vec<T, D>(a.E, s.m[c], gv);
+#pragma unroll
+        for (int i = 0; i < D; ++i) s.m[c][i] = gv[i] + a.g[c][i];
+    }
+    mat_mul_sym<T, D>(a.E, s.P, X);
+    mat_mul_t_sym<T, D>(X, a.E, a.L, Ls);
+#pragma unroll
+    for (int i = 0; i < Dim<D>::SYM; ++i) s.P[i] = Ls[i];
+}
+
+// rts_step for MC columns: fP, Pp, FP shared; f_m, mp (MC, D) per column
+template <typename T, int D, int MC>
+PGPS_HD void rts_step_m(const T (*fm)[D], const T* fP /*sym*/, const T (*mp)[D], const T* Pp, const T* FP,
+                        MeanCovM<T, D, MC>& s) {
+    T E[D * D], dP[Dim<D>::SYM], X[D * D];
+    smth_gain<T, D>(FP, Pp, E);
+#pragma unroll
+    for (int c = 0; c < MC; ++c) {
+        T dm[D], Em[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) dm[i] = s.m[c][i] - mp[c][i];
+        mat_vec<T, D>(E, dm, Em);
+#pragma unroll
+        for (int i = 0; i < D; ++i) s.m[c][i] = fm[c][i] + Em[i];
+    }
+#pragma unroll
+    for (int i = 0; i < Dim<D>::SYM; ++i) dP[i] = s.P[i] - Pp[i];
+    mat_mul_sym<T, D>(E, dP, X);
+    mat_mul_t_sym<T, D>(X, E, fP, s.P);
+}
+
 }  // namespace pgps

@@ -145,6 +145,12 @@ def _declare(lib):
         for dev in ("", "_dev"):
             getattr(lib, f"pgps_lti_ll_grad_batch{dev}_f64").argtypes = [P, c_int, c_long, c_int, P, P, P, c_double, P]
         lib.pgps_series_lti_ll_grad_batch_f64.argtypes = [P, c_int, c_int, P, P]
+    if hasattr(lib, "pgps_gp_predict_multi_f64"):       # (absent from libraries built before the multi-output scan)
+        for dev in ("", "_dev"):
+            getattr(lib, f"pgps_gp_ll_multi{dev}_f64").argtypes = [P, c_long, c_int, c_int, c_double, P, P, P, P, c_double, P, P,
+                                                                  c_double, P]
+            getattr(lib, f"pgps_gp_predict_multi{dev}_f64").argtypes = [P, c_long, c_long, c_int, c_int, c_double, P, P, P, P,
+                                                                       c_double, P, P, c_double, P, P, P, P]
     return lib
 
 
@@ -729,6 +735,43 @@ def gp_predict(form, Pinf, H, R, ts, ys, tq, t0=0.0, device=0):
                              c_double(float(t0)), _ptr(tq_a), _ptr(mean), _ptr(var),
                              ctypes.cast(ctypes.byref(ll), c_void_p))
     return mean, var, ll.value
+
+
+def _multi_inputs(form, Pinf, H, ts, Y):
+    lam, N1, N2 = form
+    ts_a = _prep(ts, np.float64, (-1,))
+    Y_a = np.ascontiguousarray(Y, dtype=np.float64)
+    if Y_a.ndim != 2 or Y_a.shape[0] != ts_a.shape[0]:
+        raise ValueError(f"observations must be (N, M) with N = {ts_a.shape[0]} rows, got shape {Y_a.shape}")
+    d = N1.shape[0]
+    model = (c_double(lam), _ptr(_prep(N1, np.float64)), _ptr(_prep(N2, np.float64)), _ptr(_prep(Pinf, np.float64, (d, d))),
+             _ptr(_prep(H, np.float64, (d,))))
+    return ts_a, Y_a, d, model
+
+
+def gp_ll_multi(form, Pinf, H, R, ts, Y, t0=0.0, device=0):
+    """Log-likelihoods of the M columns of Y (N, M) -- M independent GPs that share the kernel, the noise and the inputs
+    -- in one covariance pass (pgps_gp_ll_multi_f64): (M,).  Every row of Y is observed in all columns or NaN in all
+    columns (a mixed row raises PgpsError with PGPS_E_INVALID)."""
+    ts_a, Y_a, d, model = _multi_inputs(form, Pinf, H, ts, Y)
+    N, M = Y_a.shape
+    ll = np.empty(M, np.float64)
+    get_context(device).call("pgps_gp_ll_multi_f64", c_long(N), c_int(M), c_int(d), *model, c_double(float(R)), _ptr(ts_a),
+                             _ptr(Y_a), c_double(float(t0)), _ptr(ll))
+    return ll
+
+
+def gp_predict_multi(form, Pinf, H, R, ts, Y, tq, t0=0.0, device=0):
+    """predict_f for the M columns of Y (N, M) in one covariance pass (pgps_gp_predict_multi_f64): the merge of the sorted
+    `ts` (N) and `tq` (K), the column-tiled fused filter + smoother over the N + K steps, the projection at the K query
+    times.  Returns (mean (K, M), var (K,) -- the same for every column --, ll (M,))."""
+    ts_a, Y_a, d, model = _multi_inputs(form, Pinf, H, ts, Y)
+    tq_a = _prep(tq, np.float64, (-1,))
+    (N, M), K = Y_a.shape, tq_a.shape[0]
+    mean, var, ll = np.empty((K, M), np.float64), np.empty(K, np.float64), np.empty(M, np.float64)
+    get_context(device).call("pgps_gp_predict_multi_f64", c_long(N), c_long(K), c_int(M), c_int(d), *model, c_double(float(R)),
+                             _ptr(ts_a), _ptr(Y_a), c_double(float(t0)), _ptr(tq_a), _ptr(mean), _ptr(var), _ptr(ll))
+    return mean, var, ll
 
 
 # state dimensions of the general-LTI device path: row-cooperative kernels up to 16 (batched evaluation only there),

@@ -76,6 +76,33 @@ def _public_evaluation(fn):
     return wrapper
 
 
+def _single_output_only(fn):
+    """The evaluations that exist for one output column only: NotImplementedError for num_latent_gps > 1."""
+    import functools
+
+    @functools.wraps(fn)
+    def wrapper(self, *args, **kwargs):
+        if self.num_latent_gps > 1:
+            raise NotImplementedError(f"{fn.__name__} covers single-output models; this one has {self.num_latent_gps} output columns")
+        return fn(self, *args, **kwargs)
+    return wrapper
+
+
+def _multi_output(route):
+    """A model with num_latent_gps > 1 answers this evaluation with its method `route`; a single-output model runs the decorated
+    function exactly as before."""
+    def deco(fn):
+        import functools
+
+        @functools.wraps(fn)
+        def wrapper(self, *args, **kwargs):
+            if self.num_latent_gps > 1:
+                return getattr(self, route)(*args, **kwargs)
+            return fn(self, *args, **kwargs)
+        return wrapper
+    return deco
+
+
 def _host_discretise(F, P0, ts, t0=0.0):
     """Fs[k] = expm(dt_k F), Qs[k] = sym(P0 - Fs[k] P0 Fs[k]^T) on the host in fp64 (P0 stationary), dts = diff([t0; ts]):
     what _backend.discretise computes on the device, for the evaluations that stay on the host throughout."""
@@ -96,6 +123,19 @@ def _host_discretise(F, P0, ts, t0=0.0):
 
 
 class StateSpaceGP:
+    """GP regression on one input (time) axis.  Y (N, 1) is the reference's model.  Y (N, M) with M > 1 has GPflow's meaning of
+    that layout: M independent GPs that share the kernel, the noise variance and the inputs; num_latent_gps = M is fixed at
+    construction.  Two routes serve M > 1, and nothing falls from the first to the second on a failure (a PgpsError
+    propagates):
+      device route   parallel=True, a single Matern-1/2, -3/2 or -5/2 kernel, float64, sorted training (and query) times, and
+                     every row of Y observed in all columns or NaN in all columns: ONE covariance pass for all columns
+                     (_backend.gp_predict_multi / gp_ll_multi -- covariances, gains and innovation variances do not depend on y);
+      column loop    everything else (parallel=False, float32, RBF / Periodic / sums / products, rows with NaN in some columns
+                     only): M internal single-column models that share the kernel object, built once per data assignment,
+                     correct for any missing pattern, M full passes.
+    log_likelihood_and_grad always takes the column loop (exact; a multi-column adjoint pass does not exist yet);
+    predict_f_samples, predict_f_batch, log_likelihood_batch and log_likelihood_and_grad_batch are single-output."""
+
     def __init__(self, data, kernel, noise_variance=1.0, parallel=False, max_parallel=10000):
         self.noise_variance = float(noise_variance)
         dtype = config.default_float()
@@ -106,8 +146,8 @@ class StateSpaceGP:
             ts = ts[:, None]
         if ys.ndim == 1:
             ys = ys[:, None]
-        if ys.shape[1] != 1:
-            raise ValueError("only single-output observations are supported (pssgp/model.py:72)")
+        if ys.ndim != 2 or ys.shape[1] < 1:
+            raise ValueError(f"observations must be (N,) or (N, M) with M >= 1, got shape {ys.shape}")
         self.kernel = kernel
         self._data = ts, ys
         self.num_latent_gps = ys.shape[-1]
@@ -136,9 +176,11 @@ class StateSpaceGP:
             ts = ts[:, None]
         if ys.ndim == 1:
             ys = ys[:, None]
-        if ys.shape[1] != 1:
-            raise ValueError("only single-output observations are supported (pssgp/model.py:72)")
+        if ys.ndim != 2 or ys.shape[1] != self.num_latent_gps:
+            raise ValueError(f"the model has {self.num_latent_gps} output column(s) (fixed at construction), the new "
+                             f"observations have shape {ys.shape}")
         self._data = ts, ys
+        self._columns = None
         self.invalidate_device_series()
 
     @staticmethod
@@ -173,6 +215,84 @@ class StateSpaceGP:
         key = (struct[3], config.NUMBER_OF_BALANCING_STEPS) + vals
         self._key_memo = (version, self.kernel, config.NUMBER_OF_BALANCING_STEPS, key, tree)
         return key
+
+    # -- several outputs on one clock (num_latent_gps > 1) -----------------------------------------
+    def _column_models(self):
+        """The column loop's M single-column models: they share the kernel object and follow the noise variance; built once
+        per data assignment (and again when the arrays are found replaced or edited)."""
+        ts, ys = self.data
+        stamp = self._data_stamp(ts, ys)
+        cols = getattr(self, "_columns", None)
+        if cols is None or cols[0] != stamp:
+            models = [StateSpaceGP((ts, np.ascontiguousarray(ys[:, j:j + 1])), self.kernel, self.noise_variance,
+                                   parallel=self.parallel, max_parallel=self.max_parallel) for j in range(ys.shape[1])]
+            cols = self._columns = (stamp, models)
+        for m in cols[1]:
+            m.kernel = self.kernel
+            m.noise_variance = self.noise_variance
+        return cols[1]
+
+    def _rows_all_or_none(self):
+        """Every row of Y observed in all columns or NaN in all columns (then the columns share their covariances)?"""
+        nan = np.isnan(self.data[1])
+        return bool(np.all(nan.all(axis=1) == nan.any(axis=1)))
+
+    def _multi_device_route(self, tq=None):
+        """The fused model (sde-like, form) when the multi-column device route applies, else None (class docstring)."""
+        ts, ys = self.data
+        if not self.parallel or ys.dtype != np.float64 or ts.shape[0] < 1:
+            return None
+        fused = self._matern_forms()
+        if fused is None or not np.all(np.diff(ts.reshape(-1)) >= 0):
+            return None
+        if tq is not None and (tq.size < 1 or tq.dtype != np.float64 or not np.all(np.diff(tq) >= 0)):
+            return None
+        return fused if self._rows_all_or_none() else None
+
+    def log_likelihood_columns(self):
+        """The marginal log-likelihood of every output column, (M,); maximum_log_likelihood_objective() is their sum."""
+        if self.num_latent_gps == 1:
+            return np.asarray([self.maximum_log_likelihood_objective()], dtype=config.default_float())
+        fused = self._multi_device_route()
+        if fused is not None:
+            from . import _backend
+            sde, form = fused
+            ts, Y = self.data
+            return _backend.gp_ll_multi(form, sde.P0, sde.H, self.noise_variance, ts.reshape(-1), Y)
+        return np.asarray([m.maximum_log_likelihood_objective() for m in self._column_models()], dtype=config.default_float())
+
+    def _multi_objective(self):
+        return config.default_float()(np.sum(self.log_likelihood_columns()))
+
+    def _multi_predict_f(self, Xnew, full_cov=False, full_output_cov=False):
+        """predict_f for M > 1: mean (K, M) and var (K, M) (on the device route one variance, repeated, as GPflow returns
+        it); full_cov=True: mean (K, M) and cov (M, K, K) -- computed once on the single-output path and broadcast (a read-only
+        view) when the columns share their missing rows, per column otherwise."""
+        del full_output_cov
+        dtype = config.default_float()
+        tq = np.asarray(Xnew, dtype=dtype).reshape(-1)
+        M = self.num_latent_gps
+        if full_cov:
+            mean, _ = self._multi_predict_f(Xnew)
+            cols = self._column_models()
+            if self._rows_all_or_none():
+                cov = cols[0].predict_f(Xnew, full_cov=True)[1]
+                return mean, np.broadcast_to(cov, (M,) + cov.shape[1:])
+            return mean, np.concatenate([m.predict_f(Xnew, full_cov=True)[1] for m in cols], axis=0)
+        fused = self._multi_device_route(tq)
+        if fused is not None:
+            from . import _backend
+            sde, form = fused
+            ts, Y = self.data
+            mean, var, _ = _backend.gp_predict_multi(form, sde.P0, sde.H, self.noise_variance, ts.reshape(-1), Y, tq)
+            return mean, np.repeat(var[:, None], M, axis=1)
+        out = [m.predict_f(Xnew) for m in self._column_models()]
+        return np.concatenate([o[0] for o in out], axis=1), np.concatenate([o[1] for o in out], axis=1)
+
+    def _multi_ll_and_grad(self, wrt=None, method=None):
+        """log_likelihood_and_grad for M > 1: the sum of the per-column results (exact; M passes)."""
+        out = [m.log_likelihood_and_grad(wrt=wrt, method=method) for m in self._column_models()]
+        return config.default_float()(np.sum([o[0] for o in out])), np.sum([o[1] for o in out], axis=0)
 
     def _device_series(self, force=False):
         """The training series resident on the device (pgps_series_*, fp64 fused path): created at the SECOND evaluation of
@@ -372,6 +492,7 @@ class StateSpaceGP:
         R = np.reshape(np.asarray(self.noise_variance, dtype=config.default_float()), (1, 1))
         return self.kernel.get_ssm(ts, R)
 
+    @_multi_output("_multi_predict_f")
     @_public_evaluation
     def predict_f(self, Xnew, full_cov=False, full_output_cov=False):
         """Posterior mean (K, 1) and variance (K, 1) at `Xnew` (pssgp/model.py:92-111):
@@ -478,6 +599,7 @@ class StateSpaceGP:
             cov = sequential.ks_cov(ssm, fPs, sPs, rows, H=h)
         return mean[inverse][:, None].astype(dtype), cov[np.ix_(inverse, inverse)][None].astype(dtype)
 
+    @_single_output_only
     @_public_evaluation
     def predict_f_samples(self, Xnew, num_samples=None, full_cov=True, full_output_cov=False, seed=None):
         """Joint posterior draws of f at `Xnew` (GPflow's predict_f_samples): (S, K, 1), or (K, 1) when num_samples is
@@ -521,6 +643,7 @@ class StateSpaceGP:
         out = f[:, :, None].astype(dtype)
         return out[0] if num_samples is None else out
 
+    @_multi_output("_multi_objective")
     @_public_evaluation
     def maximum_log_likelihood_objective(self):
         ts, Y = self.data
@@ -843,6 +966,7 @@ class StateSpaceGP:
             g = np.where(keep, g, 0.0)
         return config.default_float()(stats[0]), g
 
+    @_multi_output("_multi_ll_and_grad")
     @_public_evaluation
     def log_likelihood_and_grad(self, wrt=None, method=None):
         """(ll, grad): the marginal log-likelihood and its gradient with respect to
@@ -1028,6 +1152,7 @@ class StateSpaceGP:
                 visit(b, form, F, P0, H)
         return thetas.shape[0]
 
+    @_single_output_only
     @_public_evaluation
     def log_likelihood_batch(self, thetas):
         """Marginal log-likelihoods at B hyper-parameter settings in one call: `thetas` is (B, P) in the
@@ -1096,6 +1221,7 @@ class StateSpaceGP:
         mix = np.sum(w[:, None] * mean, axis=0)
         return mix, np.sum(w[:, None] * (var + (mean - mix[None, :]) ** 2), axis=0)
 
+    @_single_output_only
     @_public_evaluation
     def predict_f_batch(self, Xnew, thetas, return_log_likelihood=False, reduce=None, weights=None):
         """predict_f at B hyper-parameter settings over the same series and query grid: `thetas` is (B, P) in the order of
@@ -1354,6 +1480,7 @@ class StateSpaceGP:
                 lls[b], grads[b] = self.log_likelihood_and_grad(wrt=wrt)
         return lls, grads
 
+    @_single_output_only
     @_public_evaluation
     def log_likelihood_and_grad_batch(self, thetas, wrt=None):
         """(lls (B,), grads (B, P)): the marginal log-likelihood and its exact gradient at B hyper-parameter settings,
