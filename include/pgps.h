@@ -712,6 +712,21 @@ int pgps_gp_predict_multi_f64(pgps_ctx*, long N, long K, int M, int d, double la
 int pgps_gp_predict_multi_dev_f64(pgps_ctx*, long N, long K, int M, int d, double lam, const double* N1, const double* N2,
                                   const double* Pinf, const double* H, double R, const double* ts, const double* ys,
                                   double t0, const double* tq, double* mean, double* var, double* ll);
+/* Log-likelihoods and the model's adjoints of the M columns in ONE filter pass and ONE reverse pass (csrc/pgps_multi_grad.hip.h):
+ *   out = [ll (M) | Abar (d d) | Ubar (d) | Hbar (d) | Rbar]
+ * ll[j] as pgps_gp_ll_multi_*; the statistics are those of pgps_series_gp_ll_grad_adj_f64 SUMMED over the columns, i.e. the
+ * adjoints of sum_j ll[j] -- the contraction with the model's derivatives is linear in them (d ll / d l = -<Abar, F> / l,
+ * d ll / d s2 = Ubar^T Pinf H^T / s2, d ll / d R = Rbar).  The reverse sweep carries one a = d ll / d m per column and ONE
+ * B = d ll / d P for the tile, so its matrix work is done once per tile of columns.  Rows of ys, errors and the _dev form
+ * (device pointers for ts, ys, out; returns with the launches enqueued; all-or-none rows are a precondition) as above; the
+ * host-array form returns PGPS_E_NUMERIC when some ll[j] is not finite.  Workgroup partials are summed in a fixed order: results
+ * repeat bit for bit and do not depend on how pgps_set_batch_scratch splits the column tiles into rounds. */
+int pgps_gp_ll_grad_multi_f64(pgps_ctx*, long N, int M, int d, double lam, const double* N1, const double* N2,
+                              const double* Pinf, const double* H, double R, const double* ts, const double* ys, double t0,
+                              double* out);
+int pgps_gp_ll_grad_multi_dev_f64(pgps_ctx*, long N, int M, int d, double lam, const double* N1, const double* N2,
+                                  const double* Pinf, const double* H, double R, const double* ts, const double* ys, double t0,
+                                  double* out);
 
 #ifdef __cplusplus
 }

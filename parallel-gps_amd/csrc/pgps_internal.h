@@ -332,6 +332,11 @@ struct GpMultiArgs {
 // (M, N), carves the scratch and runs the column groups in rounds that fit the context's batch budget
 template <int D>
 int launch_gp_multi(pgps_ctx* ctx, GpMultiArgs a, int predict, double* ll);
+// log-likelihoods and the model's adjoints summed over the columns (pgps_multi_grad.hip.h, pgps_multi_grad_inst.hip): a.N, a.M,
+// a.m, a.R, a.ys set by the caller (training steps only); out (M + d^2 + 2 d + 1) [device] = [ll (M) | Abar | Ubar | Hbar | Rbar].
+// Geometry and rounds as launch_gp_multi
+template <int D>
+int launch_gp_multi_grad(pgps_ctx* ctx, GpMultiArgs a, double* out);
 
 // merge of two sorted time arrays on the device + NaN marking of the query rows (pgps_core.hip)
 template <typename T>

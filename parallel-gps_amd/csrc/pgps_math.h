@@ -1539,4 +1539,197 @@ PGPS_HD void rts_step_m(const T (*fm)[D], const T* fP /*sym*/, const T (*mp)[D],
     mat_mul_t_sym<T, D>(X, E, fP, s.P);
 }
 
+// ------------------------------------------------------------------------------------
+// The adjoint pass (log-likelihood gradient) on a column tile: pgps_multi_grad.hip.h and tests/cpu_math/multi_adj.cpp.
+// With a_c = d ll / d m per column and B = d ll / d P SUMMED over the columns (P is shared), every matrix of the reverse
+// sweep is shared: F, Pp, u, s, K of a step, E = A^T and L of its scan element, B itself.  Per column: mp_c, r_c, a_c, g_c.
+// `nc` counts the columns of the tile that exist: the covariance-only terms (-nc / (2 s), L) are counted nc times; an absent
+// column carries y = 0 and keeps r_c = a_c = 0, so it adds nothing to any sum over c.
+// ------------------------------------------------------------------------------------
+// one step's quantities from the state entering it (the arithmetic of adj_step in pgps_gpadj.hip.h, once per tile)
+template <typename T, int D, int MC>
+struct AdjStepM {
+    T F[D * D], Pp[Dim<D>::SYM], u[D], K[D];
+    T mp[MC][D], r[MC];
+    T S, inv;
+    bool obs;
+};
+
+template <typename T, int D, int MC>
+PGPS_HD void adj_step_m(const T* F, const T* Q /*sym*/, const MeanCovM<T, D, MC>& s, const T* y /*MC*/, bool obs, const T* h, T R,
+                        AdjStepM<T, D, MC>& o) {
+    T FP[D * D];
+#pragma unroll
+    for (int i = 0; i < D * D; ++i) o.F[i] = F[i];
+#pragma unroll
+    for (int c = 0; c < MC; ++c) mat_vec<T, D>(F, s.m[c], o.mp[c]);
+    predict_cov<T, D>(F, s.P, Q, FP, o.Pp);
+    sym_vec<T, D>(o.Pp, h, o.u);
+    T S = R;
+#pragma unroll
+    for (int i = 0; i < D; ++i) S += h[i] * o.u[i];
+    o.obs = obs;
+    o.S = S;
+    o.inv = obs ? recip(S) : T(0);
+#pragma unroll
+    for (int c = 0; c < MC; ++c) {
+        T mu = T(0);
+#pragma unroll
+        for (int i = 0; i < D; ++i) mu += h[i] * o.mp[c][i];
+        o.r[c] = obs ? y[c] - mu : T(0);
+    }
+#pragma unroll
+    for (int i = 0; i < D; ++i) o.K[i] = o.u[i] * o.inv;
+}
+
+// the filtered state of the step
+template <typename T, int D, int MC>
+PGPS_HD void adj_filtered_m(const AdjStepM<T, D, MC>& st, MeanCovM<T, D, MC>& s) {
+#pragma unroll
+    for (int c = 0; c < MC; ++c)
+#pragma unroll
+        for (int i = 0; i < D; ++i) s.m[c][i] = st.mp[c][i] + st.K[i] * st.r[c];
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = i; j < D; ++j) s.P[symi<D>(i, j)] = st.Pp[symi<D>(i, j)] - st.u[i] * st.u[j] * st.inv;
+}
+
+// the step's adjoint element:  E = A^T (A = (I - K H) F),  g_c = v r_c / s,  L = -nc v v^T / (2 s),  v = F^T H^T; a missing
+// step has inv = 0 and r = 0: E = F^T, g = 0, L = 0.  E, and L / nc, are the single-column element's bit for bit.
+template <typename T, int D, int MC>
+PGPS_HD void adj_element_m(const AdjStepM<T, D, MC>& st, const T* h, int nc, SmthElemM<T, D, MC>& e) {
+    T v[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        T acc = T(0);
+#pragma unroll
+        for (int i = 0; i < D; ++i) acc += h[i] * st.F[i * D + j];
+        v[j] = acc;
+    }
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) e.E[j * D + i] = st.F[i * D + j] - st.K[i] * v[j];
+#pragma unroll
+    for (int c = 0; c < MC; ++c)
+#pragma unroll
+        for (int j = 0; j < D; ++j) e.g[c][j] = v[j] * (st.r[c] * st.inv);
+    const T fn = T(nc);
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = i; j < D; ++j) e.L[symi<D>(i, j)] = (T(-0.5) * v[i] * v[j] * st.inv) * fn;
+}
+
+// (a_c, W) behind a step -> (a_c, B):  B = W + (1/2) sum_c a_c a_c^T
+template <typename T, int D, int MC>
+PGPS_HD void adj_cov_from_scan_m(const MeanCovM<T, D, MC>& z, T* B /*sym*/) {
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = i; j < D; ++j) {
+            T acc = T(0);
+#pragma unroll
+            for (int c = 0; c < MC; ++c) acc += z.m[c][i] * z.m[c][j];
+            B[symi<D>(i, j)] = z.P[symi<D>(i, j)] + T(0.5) * acc;
+        }
+}
+
+// the reverse step: st = [Abar (D D) | Ubar (D) | Hbar (D) | Rbar] += the step's terms (summed over the columns), then
+// a_c <- F^T mpbar_c,  B <- sym(F^T Ppbar F)
+template <typename T, int D, int MC>
+PGPS_HD void adj_reverse_m(const AdjStepM<T, D, MC>& q, T dt, const T* h, const T* Pinf /*sym*/, int nc, T (*av)[D], T* B /*sym*/,
+                           T* st) {
+    constexpr int MAT = D * D, SYM = Dim<D>::SYM;
+    T* Abar = st;
+    T* Ubar = st + MAT;
+    T* Hbar = st + MAT + D;
+    T& Rbar = st[MAT + 2 * D];
+    T BK[D], ubar[D], Ppbar[SYM], mpbar[MC][D], rbar[MC];
+    sym_vec<T, D>(B, q.K, BK);
+    T KBK = T(0);
+#pragma unroll
+    for (int i = 0; i < D; ++i) KBK += q.K[i] * BK[i];
+    T quad = T(0), ari[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) ari[i] = T(0);
+#pragma unroll
+    for (int c = 0; c < MC; ++c) {
+        T aK = T(0);
+#pragma unroll
+        for (int i = 0; i < D; ++i) aK += av[c][i] * q.K[i];
+        const T ri = q.r[c] * q.inv;
+        quad += -aK * ri + T(0.5) * ri * ri;
+        rbar[c] = q.obs ? (aK - ri) : T(0);
+#pragma unroll
+        for (int i = 0; i < D; ++i) ari[i] += av[c][i] * ri;
+    }
+    const T sbar = q.obs ? (quad + KBK - T(0.5) * T(nc) * q.inv) : T(0);
+#pragma unroll
+    for (int i = 0; i < D; ++i) ubar[i] = q.obs ? (ari[i] - T(2) * BK[i] + sbar * h[i]) : T(0);
+#pragma unroll
+    for (int c = 0; c < MC; ++c)
+#pragma unroll
+        for (int i = 0; i < D; ++i) mpbar[c][i] = av[c][i] - rbar[c] * h[i];
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = i; j < D; ++j) Ppbar[symi<D>(i, j)] = B[symi<D>(i, j)] + T(0.5) * (ubar[i] * h[j] + h[i] * ubar[j]);
+    // Abar += dt [sum_c mpbar_c mp_c^T + 2 Ppbar (Pp - Pinf)]
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            T acc = T(0);
+#pragma unroll
+            for (int c = 0; c < MC; ++c) acc += mpbar[c][i] * q.mp[c][j];
+#pragma unroll
+            for (int l = 0; l < D; ++l) {
+                const int il = symi<D>(i < l ? i : l, i < l ? l : i), lj = symi<D>(l < j ? l : j, l < j ? j : l);
+                acc += T(2) * Ppbar[il] * (q.Pp[lj] - Pinf[lj]);
+            }
+            Abar[i * D + j] += dt * acc;
+        }
+    T Ppu[D];
+    sym_vec<T, D>(q.Pp, ubar, Ppu);
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        T rm = T(0);
+#pragma unroll
+        for (int c = 0; c < MC; ++c) rm += rbar[c] * q.mp[c][i];
+        Ubar[i] += ubar[i];
+        Hbar[i] += sbar * q.u[i] + Ppu[i] - rm;
+    }
+    Rbar += sbar;
+#pragma unroll
+    for (int c = 0; c < MC; ++c)
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            T acc = T(0);
+#pragma unroll
+            for (int l = 0; l < D; ++l) acc += q.F[l * D + i] * mpbar[c][l];
+            av[c][i] = acc;
+        }
+    T X[MAT];
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            T acc = T(0);
+#pragma unroll
+            for (int l = 0; l < D; ++l) acc += Ppbar[symi<D>(i < l ? i : l, i < l ? l : i)] * q.F[l * D + j];
+            X[i * D + j] = acc;                                         // Ppbar F
+        }
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = i; j < D; ++j) {
+            T acc = T(0), acct = T(0);
+#pragma unroll
+            for (int l = 0; l < D; ++l) { acc += q.F[l * D + i] * X[l * D + j]; acct += q.F[l * D + j] * X[l * D + i]; }
+            B[symi<D>(i, j)] = T(0.5) * (acc + acct);
+        }
+}
+
 }  // namespace pgps

@@ -1,7 +1,7 @@
 // pgps_multi_api.hip -- the multi-column entry points of the C ABI (include/pgps.h: pgps_gp_ll_multi_*,
-// pgps_gp_predict_multi_*): argument checks, the all-or-none check of the host forms, staging through the context's
-// buffers, the merge of training and query times with the source ROW of every merged step as its payload, dispatch to
-// launch_gp_multi<d> (pgps_multi_inst.hip).
+// pgps_gp_predict_multi_*, pgps_gp_ll_grad_multi_*): argument checks, the all-or-none check of the host forms, staging
+// through the context's buffers, the merge of training and query times with the source ROW of every merged step as its
+// payload, dispatch to launch_gp_multi<d> (pgps_multi_inst.hip) and launch_gp_multi_grad<d> (pgps_multi_grad_inst.hip).
 #include "pgps_host.h"
 
 using namespace pgps;
@@ -45,6 +45,17 @@ static int gp_ll_multi_dev(pgps_ctx* ctx, long N, int M, int d, double lam, cons
     if (!ll) return PGPS_E_INVALID;
     a.m.t_prev = t0;
     return multi_dispatch(ctx, d, a, 0, ll);
+}
+
+static int gp_ll_grad_multi_dev(pgps_ctx* ctx, long N, int M, int d, double lam, const double* N1, const double* N2,
+                                const double* Pinf, const double* H, double R, const double* ts, const double* ys, double t0,
+                                double* out) {
+    GpMultiArgs a;
+    TRY(multi_args(ctx, N, M, d, lam, N1, N2, Pinf, H, R, ts, ys, &a));
+    if (!out) return PGPS_E_INVALID;
+    a.m.t_prev = t0;
+    RoctxRange range_("parallel_filter");
+    return for_dim<1, 3>(d, [&](auto D) { return launch_gp_multi_grad<D()>(ctx, a, out); });
 }
 
 static int gp_predict_multi_dev(pgps_ctx* ctx, long N, long K, int M, int d, double lam, const double* N1, const double* N2,
@@ -147,4 +158,31 @@ extern "C" int pgps_gp_predict_multi_f64(pgps_ctx* ctx, long N, long K, int M, i
     TRY(stage_out(ctx, llh.data(), dll, (size_t)M));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return ll_multi_result(M, llh.data(), ll);
+}
+
+extern "C" int pgps_gp_ll_grad_multi_dev_f64(pgps_ctx* ctx, long N, int M, int d, double lam, const double* N1, const double* N2,
+                                             const double* Pinf, const double* H, double R, const double* ts, const double* ys,
+                                             double t0, double* out) {
+    return gp_ll_grad_multi_dev(ctx, N, M, d, lam, N1, N2, Pinf, H, R, ts, ys, t0, out);
+}
+
+extern "C" int pgps_gp_ll_grad_multi_f64(pgps_ctx* ctx, long N, int M, int d, double lam, const double* N1, const double* N2,
+                                         const double* Pinf, const double* H, double R, const double* ts, const double* ys,
+                                         double t0, double* out) {
+    GpMultiArgs chk;
+    TRY(multi_args(ctx, N, M, d, lam, N1, N2, Pinf, H, R, ts, ys, &chk));
+    if (!out) return PGPS_E_INVALID;
+    if (!rows_all_or_none(N, M, ys)) return PGPS_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nout = (size_t)M + (size_t)(d * d + 2 * d + 1);
+    double *dts, *dys, *dout;
+    TRY(stage_in(ctx, ctx->st[10], ts, (size_t)N, &dts));
+    TRY(stage_in(ctx, ctx->st[4], ys, (size_t)N * M, &dys));
+    TRY(stage_in<double>(ctx, ctx->st[9], nullptr, nout, &dout));
+    TRY(gp_ll_grad_multi_dev(ctx, N, M, d, lam, N1, N2, Pinf, H, R, dts, dys, t0, dout));
+    std::vector<double> outh(nout);
+    TRY(stage_out(ctx, outh.data(), dout, nout));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < nout; ++i) out[i] = outh[i];
+    return ll_multi_result(M, outh.data(), nullptr);
 }

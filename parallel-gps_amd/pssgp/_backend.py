@@ -151,6 +151,10 @@ def _declare(lib):
                                                                   c_double, P]
             getattr(lib, f"pgps_gp_predict_multi{dev}_f64").argtypes = [P, c_long, c_long, c_int, c_int, c_double, P, P, P, P,
                                                                        c_double, P, P, c_double, P, P, P, P]
+    if hasattr(lib, "pgps_gp_ll_grad_multi_f64"):       # (absent from libraries built before the multi-output adjoint pass)
+        for dev in ("", "_dev"):
+            getattr(lib, f"pgps_gp_ll_grad_multi{dev}_f64").argtypes = [P, c_long, c_int, c_int, c_double, P, P, P, P, c_double, P,
+                                                                       P, c_double, P]
     return lib
 
 
@@ -772,6 +776,23 @@ def gp_predict_multi(form, Pinf, H, R, ts, Y, tq, t0=0.0, device=0):
     get_context(device).call("pgps_gp_predict_multi_f64", c_long(N), c_long(K), c_int(M), c_int(d), *model, c_double(float(R)),
                              _ptr(ts_a), _ptr(Y_a), c_double(float(t0)), _ptr(tq_a), _ptr(mean), _ptr(var), _ptr(ll))
     return mean, var, ll
+
+
+def gp_ll_grad_multi(form, Pinf, H, R, ts, Y, t0=0.0, device=0):
+    """Log-likelihoods of the M columns of Y (N, M) and the model's adjoints SUMMED over the columns, in one filter pass and one
+    reverse pass on column tiles (pgps_gp_ll_grad_multi_f64): (ll (M,), Abar (d, d), Ubar (d,), Hbar (d,), Rbar) -- the
+    statistics of sum_j ll[j], contracted by contract_grad_stats().  Rows of Y as gp_ll_multi takes them."""
+    ts_a, Y_a, d, model = _multi_inputs(form, Pinf, H, ts, Y)
+    N, M = Y_a.shape
+    ctx = get_context(device)
+    if not hasattr(ctx.lib, "pgps_gp_ll_grad_multi_f64"):
+        raise RuntimeError("this libpgps has no pgps_gp_ll_grad_multi_* entry points")
+    out = np.zeros(M + d * d + 2 * d + 1, np.float64)
+    ctx.call("pgps_gp_ll_grad_multi_f64", c_long(N), c_int(M), c_int(d), *model, c_double(float(R)), _ptr(ts_a), _ptr(Y_a),
+             c_double(float(t0)), _ptr(out))
+    dd = d * d
+    st = out[M:]
+    return out[:M].copy(), st[:dd].reshape(d, d).copy(), st[dd:dd + d].copy(), st[dd + d:dd + 2 * d].copy(), float(st[dd + 2 * d])
 
 
 # state dimensions of the general-LTI device path: row-cooperative kernels up to 16 (batched evaluation only there),

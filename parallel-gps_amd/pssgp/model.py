@@ -133,7 +133,10 @@ class StateSpaceGP:
       column loop    everything else (parallel=False, float32, RBF / Periodic / sums / products, rows with NaN in some columns
                      only): M internal single-column models that share the kernel object, built once per data assignment,
                      correct for any missing pattern, M full passes.
-    log_likelihood_and_grad always takes the column loop (exact; a multi-column adjoint pass does not exist yet);
+    log_likelihood_and_grad takes the device route as well (method "adjoint", or method None where _multi_grad_pays() finds it
+    cheaper than the loop): ONE filter pass and ONE reverse pass on column tiles give the columns' log-likelihoods and the
+    adjoints of their sum (_backend.gp_ll_grad_multi -- the reverse sweep's matrices do not depend on y either); method
+    "dual" / "differences" and everything off the device route loop;
     predict_f_samples, predict_f_batch, log_likelihood_batch and log_likelihood_and_grad_batch are single-output."""
 
     def __init__(self, data, kernel, noise_variance=1.0, parallel=False, max_parallel=10000):
@@ -289,8 +292,47 @@ class StateSpaceGP:
         out = [m.predict_f(Xnew) for m in self._column_models()]
         return np.concatenate([o[0] for o in out], axis=1), np.concatenate([o[1] for o in out], axis=1)
 
+    def _multi_grad_pays(self, n, m):
+        """Automatic choice between ONE multi-column adjoint call (host arrays: Y is copied per call) and the column loop (M
+        single-column passes over series that are resident from a model's second evaluation on), from one run of
+        tools/multi_grad_bench.py on an MI355X (profiles/multi_grad_bench.json; medians in ms, multi / loop).
+        N = 4096, M = 2, 3, 4: Matern-1/2 0.100 / 0.073, 0.104 / 0.110, 0.097 / 0.147; Matern-3/2 0.109 / 0.095, 0.112 / 0.142,
+        0.110 / 0.190; Matern-5/2 0.144 / 0.169, 0.150 / 0.257, 0.147 / 0.334: from M = 3 (Matern-5/2: from M = 2).
+        M = 16, N = 2^15 .. 2^18, 2^20: Matern-3/2 0.27 / 0.77, 0.42 / 0.79, 0.80 / 0.81, 1.69 / 0.91, 6.64 / 1.33; Matern-5/2
+        0.32 / 1.41, 0.61 / 1.41, 1.04 / 1.43, 2.25 / 1.64, 7.41 / 2.15: the copy of Y (8 N M bytes per call) overtakes the loop's M
+        passes between 2^16 and 2^17 steps for Matern-3/2 and between 2^17 and 2^18 for Matern-5/2, whatever M (both sides
+        grow with M): up to the last length measured as a win.  Matern-1/2 was not measured there and takes Matern-3/2's
+        bound.  The passes alone (device-resident Y, pgps_gp_ll_grad_multi_dev_f64) win at every point measured."""
+        name = type(self.kernel).__name__
+        return m >= (2 if name == "Matern52" else 3) and n <= (131072 if name == "Matern52" else 65536)
+
     def _multi_ll_and_grad(self, wrt=None, method=None):
-        """log_likelihood_and_grad for M > 1: the sum of the per-column results (exact; M passes)."""
+        """log_likelihood_and_grad for M > 1.  Device route (class docstring) and method "adjoint", or method None where
+        _multi_grad_pays() says so: ONE call of _backend.gp_ll_grad_multi -- one filter pass and one reverse pass on column tiles
+        return the columns' log-likelihoods and the model's adjoints summed over the columns (csrc/pgps_multi_grad.hip.h), contracted as
+        _fused_adjoint_ll_and_grad contracts them: d ll / d l = -<Abar, F> / l, d ll / d s2 = Ubar^T Pinf H^T / s2,
+        d ll / d R = Rbar.  Everything else (method "dual" or "differences", parallel=False, float32, other kernels, rows with
+        NaN in some columns only, unsorted times): the sum of the per-column results (exact; M passes)."""
+        fused = self._multi_device_route() if method in (None, "adjoint") else None
+        if fused is not None and (method == "adjoint" or self._multi_grad_pays(self.data[0].shape[0], self.num_latent_gps)):
+            from . import _backend
+            sde, form = fused
+            ts, Y = self.data
+            lam, N1, _ = form
+            d = N1.shape[0]
+            P0 = np.asarray(sde.P0, np.float64)
+            H = np.asarray(sde.H, np.float64).reshape(-1)
+            lls, Abar, Ubar, _, Rbar = _backend.gp_ll_grad_multi(form, P0, H, self.noise_variance, ts.reshape(-1), Y)
+            F = np.asarray(N1, np.float64) - float(lam) * np.eye(d)          # F = N1 - lam I
+            k = self.kernel
+            by_name = {"variance": float(Ubar @ (P0 @ H)) / float(k.variance),
+                       "lengthscales": -float(np.sum(Abar * F)) / float(k.lengthscales)}
+            g = np.array([by_name[a] for _, a in leaf_parameters(k)] + [float(Rbar)])
+            if wrt is not None:
+                keep = np.zeros(len(g), bool)
+                keep[[int(i) for i in wrt]] = True
+                g = np.where(keep, g, 0.0)
+            return config.default_float()(np.sum(lls)), g
         out = [m.log_likelihood_and_grad(wrt=wrt, method=method) for m in self._column_models()]
         return config.default_float()(np.sum([o[0] for o in out])), np.sum([o[1] for o in out], axis=0)
 
