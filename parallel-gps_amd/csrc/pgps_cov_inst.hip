@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "pgps_cov.hip.h"
+#include "pgps_scratch.h"
 
 #ifndef PGPS_COV_T
 #error "compile with -DPGPS_COV_T=<float|double> -DPGPS_COV_D=<d>"
@@ -16,11 +17,12 @@ int launch_cov_gains(pgps_ctx* ctx, CovArgs<T> a) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     geometry(ctx, a.N, &a.Lc, &a.nblocks, D);
     a.nlanes = (long)a.nblocks * kBlock;
-    const size_t lsuf = (size_t)NREC * (size_t)a.nlanes, spine = (size_t)a.nblocks * NREC;
-    int rc = ensure(ctx, ctx->cov[0], (lsuf + spine) * sizeof(T) + 256);
-    if (rc) return rc;
-    a.lsuf = (T*)ctx->cov[0].p;
-    a.spine = a.lsuf + (lsuf + 31) / 32 * 32;
+    // the spine starts on a whole 32 elements behind the lane suffixes (those are whole 256-lane rows)
+    Carver c(32 * sizeof(T));
+    const auto lsuf = c.part<T>((size_t)NREC * (size_t)a.nlanes), spine = c.part<T>((size_t)a.nblocks * NREC);
+    Scratch s;
+    if (int rc = commit(ctx, ctx->cov[0], c, &s)) return rc;
+    a.lsuf = s(lsuf); a.spine = s(spine);
     const dim3 grid(a.nblocks), block(kBlock);
     hipLaunchKernelGGL((k_cov_reduce<T, D>), grid, block, 0, ctx->stream, a);
     hipLaunchKernelGGL((k_cov_apply<T, D>), grid, block, 0, ctx->stream, a);
@@ -35,11 +37,11 @@ int launch_cov_fill(pgps_ctx* ctx, CovFillArgs<T> a) {
     const long nt = (a.n + kCovTile - 1) / kCovTile;
     if (nt > 65535) return PGPS_E_INVALID;
     a.nt = (int)nt;
-    const size_t nU = ((size_t)a.n * MAT + 31) / 32 * 32;
-    int rc = ensure(ctx, ctx->cov[4], (nU + (size_t)nt * nt * MAT) * sizeof(T) + 256);
-    if (rc) return rc;
-    a.U = (T*)ctx->cov[4].p;
-    a.M = a.U + nU;
+    Carver c(32 * sizeof(T));                           // M starts on a whole 32 elements behind U
+    const auto U = c.part<T>((size_t)a.n * MAT), M = c.part<T>((size_t)nt * nt * MAT);
+    Scratch s;
+    if (int rc = commit(ctx, ctx->cov[4], c, &s)) return rc;
+    a.U = s(U); a.M = s(M);
     const dim3 wave(kCovTile);
     if (nt > 1) hipLaunchKernelGGL((k_cov_tile_prefix<T, D>), dim3((unsigned)(nt - 1)), wave, 0, ctx->stream, a);
     if (nt > 2)

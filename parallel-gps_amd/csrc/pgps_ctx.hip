@@ -460,6 +460,26 @@ void geometry_narrow(const pgps_ctx* ctx, long N, int* Lc, int* nblocks, int d) 
     *Lc = c;
     *nblocks = (int)(nb < 1 ? 1 : nb);
 }
+// B models (or column groups) over one series of N steps, (workgroups, models) grids of 256-lane workgroups -- ONE statement
+// for every batched fused launch: they promise results that do not depend on how a batch is split into groups, which holds
+// only while they agree on the geometry.  pgps_set_chunk's value, else 16 steps per lane while the batch keeps the chip
+// covered (>= 1024 workgroups: the serial part is the efficient one), halved towards 4 when B x N is small; a series shorter
+// than four steps per lane of one workgroup takes one workgroup
+int batch_steps_per_lane(const pgps_ctx* ctx, int B, long N) {
+    int lc = ctx->chunk;
+    if (lc <= 0) {
+        lc = 16;
+        while (lc > 4 && (long)B * ((N + (long)kBlock * lc - 1) / ((long)kBlock * lc)) < 1024) lc /= 2;
+        if (N < (long)kBlock * 4) lc = (int)((N + kBlock - 1) / kBlock);
+        if (lc < 1) lc = 1;
+    }
+    return lc;
+}
+// ... and the multi-output launches' steps per lane and workgroups by it, from the column groups of the whole call
+void multi_geometry(const pgps_ctx* ctx, long N, int groups_all, int* Lc, int* nblocks) {
+    *Lc = batch_steps_per_lane(ctx, groups_all, N);
+    *nblocks = (int)((N + (long)kBlock * *Lc - 1) / ((long)kBlock * *Lc));
+}
 }  // namespace pgps
 
 namespace pgps {

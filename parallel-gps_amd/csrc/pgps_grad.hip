@@ -1,5 +1,6 @@
 // pgps_grad.hip -- host side of the log-likelihood gradient (pgps_gp_ll_grad_*): see pgps_grad.hip.h.
 #include "pgps_grad.hip.h"
+#include "pgps_scratch.h"
 
 namespace pgps {
 
@@ -13,17 +14,11 @@ static int launch_grad_d(pgps_ctx* ctx, GradModel<NP> m) {
     geometry(ctx, m.N, &m.Lc, &m.nblocks);
     m.nlanes = (long)m.nblocks * kBlock;
     const size_t nb = (size_t)m.nblocks, nl = (size_t)m.nlanes;
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    size_t off = 0;
-    const size_t o_spine = off; off = up(off + nb * Dim<D>::NFILT * sizeof(T));
-    const size_t o_lpre = off;  off = up(off + nl * Dim<D>::NFILT * sizeof(T));
-    const size_t o_ll = off;    off = up(off + nb * sizeof(T));
-    int rc = ensure(ctx, ctx->ws, off);
-    if (rc) return rc;
-    char* base = (char*)ctx->ws.p;
-    m.spine = (T*)(base + o_spine);
-    m.lpre = (T*)(base + o_lpre);
-    m.llpart = (T*)(base + o_ll);
+    Carver c(256);
+    const auto spine = c.part<T>(nb * Dim<D>::NFILT), lpre = c.part<T>(nl * Dim<D>::NFILT), llpart = c.part<T>(nb);
+    Scratch s;
+    if (int rc = commit(ctx, ctx->ws, c, &s)) return rc;
+    m.spine = s(spine); m.lpre = s(lpre); m.llpart = s(llpart);
     const dim3 grid(m.nblocks), block(kBlock);
     timed_launch(ctx, PGPS_K_FILTER_REDUCE, k_grad_reduce<NP, D>, grid, block, 0, m);
     timed_launch(ctx, PGPS_K_FILTER_APPLY, k_grad_apply<NP, D>, grid, block, 0, m);
@@ -76,20 +71,21 @@ static int launch_grad_pack(pgps_ctx* ctx, long N, int np, const double* model, 
     if (ctx->chunk <= 0 && N <= kGradOneLaunch && nblocks > 1) { Lc = (int)((N + kBlock - 1) / kBlock); nblocks = 1; }
     nlanes = (long)nblocks * kBlock;
     const size_t nb = (size_t)nblocks, nl = (size_t)nlanes;
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t s_spine = up(nb * Dim<D>::NFILT * sizeof(T)), s_lpre = up(nl * Dim<D>::NFILT * sizeof(T)), s_ll = up(nb * sizeof(T));
-    const size_t per = s_spine + s_lpre + s_ll;
-    int rc = ensure(ctx, ctx->ws, per * (size_t)np + 256);
-    if (rc) return rc;
-    char* base = (char*)ctx->ws.p;
-    double* scratch = (double*)(base + per * (size_t)np);
+    // the np models' records one after the other, then the (ll, d ll / d theta_p) pairs the passes write
+    Carver c(256);
+    Part<T> spine[3], lpre[3], llpart[3];
+    for (int p = 0; p < np; ++p) {
+        spine[p] = c.part<T>(nb * Dim<D>::NFILT); lpre[p] = c.part<T>(nl * Dim<D>::NFILT); llpart[p] = c.part<T>(nb);
+    }
+    const auto pairs = c.part<double>(2 * (size_t)np);
+    Scratch s;
+    if (int rc = commit(ctx, ctx->ws, c, &s)) return rc;
+    double* scratch = s(pairs);
     for (int p = 0; p < 3; ++p) pack.m[p] = make_model<1>(D, np, p < np ? p : 0, model, N, ts, t0, ys, scratch + 2 * (p < np ? p : 0));
     for (int p = 0; p < np; ++p) {
         GradModel<1>& m = pack.m[p];
         m.Lc = Lc; m.nblocks = nblocks; m.nlanes = nlanes;
-        m.spine = (T*)(base + per * p);
-        m.lpre = (T*)(base + per * p + s_spine);
-        m.llpart = (T*)(base + per * p + s_spine + s_lpre);
+        m.spine = s(spine[p]); m.lpre = s(lpre[p]); m.llpart = s(llpart[p]);
     }
     const dim3 grid(nblocks, np), block(kBlock);
     if (nblocks == 1) {

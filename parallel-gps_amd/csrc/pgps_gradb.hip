@@ -8,6 +8,7 @@
 // `Matern32 + Matern52` and `Matern32 * Matern52` (tests/test_gp_vs_kfs.py:40-41,53-78).  One direction per pass (a
 // dual filtering element at d = 6 is already 180 doubles per lane); compiled one unit per d (-DPGPS_GRADB_D).
 #include "pgps_grad.hip.h"
+#include "pgps_scratch.h"
 
 #ifndef PGPS_GRADB_D
 #error "compile with -DPGPS_GRADB_D=<d>"
@@ -211,15 +212,11 @@ int launch_gradb(pgps_ctx* ctx, long N, int nblk, const int* bsize, int np, cons
         m.nblocks = (int)((N + (long)kBlock * m.Lc - 1) / ((long)kBlock * m.Lc));
         m.nlanes = (long)m.nblocks * kBlock;
         const size_t nb = (size_t)m.nblocks, nl = (size_t)m.nlanes;
-        auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-        size_t off = 0;
-        const size_t o_spine = off; off = up(off + nb * Dim<D>::NFILT * sizeof(T));
-        const size_t o_lpre = off;  off = up(off + nl * Dim<D>::NFILT * sizeof(T));
-        const size_t o_ll = off;    off = up(off + nb * sizeof(T));
-        int rc = ensure(ctx, ctx->ws, off);
-        if (rc) return rc;
-        char* base = (char*)ctx->ws.p;
-        m.spine = (T*)(base + o_spine); m.lpre = (T*)(base + o_lpre); m.llpart = (T*)(base + o_ll);
+        Carver c(256);
+        const auto spine = c.part<T>(nb * Dim<D>::NFILT), lpre = c.part<T>(nl * Dim<D>::NFILT), llpart = c.part<T>(nb);
+        Scratch s;
+        if (int rc = commit(ctx, ctx->ws, c, &s)) return rc;
+        m.spine = s(spine); m.lpre = s(lpre); m.llpart = s(llpart);
         const dim3 grid(m.nblocks), block(kBlock);
         timed_launch(ctx, PGPS_K_FILTER_REDUCE, k_gradb_reduce<D>, grid, block, 0, m);
         timed_launch(ctx, PGPS_K_FILTER_APPLY, k_gradb_apply<D>, grid, block, 0, m);

@@ -27,6 +27,8 @@
 
 #include <type_traits>
 
+#include "pgps_scratch.h"
+
 #ifndef PGPS_INST_T
 #error "compile with -DPGPS_INST_T=<float|double> -DPGPS_INST_D=<d>"
 #endif
@@ -38,38 +40,28 @@
 
 namespace pgps {
 
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 template <typename T, int D>
 static int carve_workspace(pgps_ctx* ctx, ScanArgs<T>& a) {
     const size_t nl = (size_t)a.nlanes, nb = (size_t)a.nblocks;
-    size_t off = 0;
-    const size_t o_spine = off;  off = align_up(off + nb * Dim<D>::NFILT * sizeof(T), 256);
-    const size_t o_lpre = off;   off = align_up(off + nl * Dim<D>::NFILT * sizeof(T), 256);
-    const size_t o_sspine = off; off = align_up(off + nb * Dim<D>::NSMTH * sizeof(T), 256);
-    const size_t o_lsuf = off;   off = align_up(off + nl * Dim<D>::NSMTH * sizeof(T), 256);
-    const size_t o_ll = off;     off = align_up(off + nb * sizeof(double), 256);
-    const size_t o_status = off; off = align_up(off + 16, 256);
-    const size_t o_seg = off;    off = align_up(off + (2 * (size_t)(D + D * D) + 2 * D * D) * sizeof(T), 256);
-    const size_t o_flags = off;  off = align_up(off + (nb + 4 + 8 * 32) * sizeof(int), 256);       // (ticket +) the single-pass barrier's counter shards
-    const size_t o_incl = off;   off = align_up(off + nb * Dim<D>::NMP * sizeof(T), 256);
-    int rc = ensure(ctx, ctx->ws, off);
-    if (rc) return rc;
-    char* base = (char*)ctx->ws.p;
-    a.spine = (T*)(base + o_spine);
-    a.lpre = (T*)(base + o_lpre);
-    a.sspine = (T*)(base + o_sspine);
-    a.lsuf = (T*)(base + o_lsuf);
-    a.llpart = (double*)(base + o_ll);
+    Carver c(256);
+    const auto spine = c.part<T>(nb * Dim<D>::NFILT), lpre = c.part<T>(nl * Dim<D>::NFILT);
+    const auto sspine = c.part<T>(nb * Dim<D>::NSMTH), lsuf = c.part<T>(nl * Dim<D>::NSMTH);
+    const auto ll = c.part<double>(nb);
+    c.part<char>(16);                                                   // reserved (the status word lives in the context)
+    const auto seg = c.part<T>(2 * (size_t)(D + D * D) + 2 * D * D);
+    const auto flags = c.part<int>(nb + 4 + 8 * 32);                    // (ticket +) the single-pass barrier's counter shards
+    const auto incl = c.part<T>(nb * Dim<D>::NMP);
+    Scratch s;
+    if (int rc = commit(ctx, ctx->ws, c, &s)) return rc;
+    a.spine = s(spine); a.lpre = s(lpre); a.sspine = s(sspine); a.lsuf = s(lsuf);
+    a.llpart = s(ll);
     a.status = ctx->status_word;
-    (void)o_status;
-    a.seg_ws = (T*)(base + o_seg);
-    a.ticket = (int*)(base + o_flags);
+    a.seg_ws = s(seg);
+    a.ticket = s(flags);
     a.flags = a.ticket + 4;
-    a.incl = (T*)(base + o_incl);
+    a.incl = s(incl);
 #ifdef PGPS_STAMPS
-    rc = ensure(ctx, ctx->stamps, (size_t)3 * nb * 8 * sizeof(long long));
-    if (rc) return rc;
+    if (int rc = ensure(ctx, ctx->stamps, (size_t)3 * nb * 8 * sizeof(long long))) return rc;
     a.stamps = (long long*)ctx->stamps.p;
 #endif
     return PGPS_OK;
@@ -255,25 +247,11 @@ int launch_disc(pgps_ctx* ctx, long N, const T* F, const T* Pinf, const T* ts, T
 }
 
 // ---- fused-discretisation ("gp") launches: d <= 3 ------------------------------------------------------
-// The two geometry rules every fused launcher shares (one statement each: the batched calls promise results that do not
-// depend on how a batch is split, which holds only while they agree on the geometry).
-// One workgroup walks the whole series: steps per lane, rounded up to whole 4-step sub-tiles
+// One workgroup walks the whole series: steps per lane, rounded up to whole 4-step sub-tiles (the other geometry rule the fused
+// launchers share, batch_steps_per_lane, is the context's: pgps_ctx.hip)
 static inline long one_workgroup_steps(long N) {
     const long v = (N + kBlock - 1) / kBlock;
     return (v + 3) / 4 * 4;
-}
-// B models over one series of N steps, (workgroups, models) grids: pgps_set_chunk's value, else 16 steps per lane while the
-// batch keeps the chip covered (>= 1024 workgroups: the serial part is the efficient one), halved towards 4 when B x N is
-// small; a series shorter than four steps per lane of one workgroup takes one workgroup
-static inline int batch_steps_per_lane(const pgps_ctx* ctx, int B, long N) {
-    int lc = ctx->chunk;
-    if (lc <= 0) {
-        lc = 16;
-        while (lc > 4 && (long)B * ((N + (long)kBlock * lc - 1) / ((long)kBlock * lc)) < 1024) lc /= 2;
-        if (N < (long)kBlock * 4) lc = (int)((N + kBlock - 1) / kBlock);
-        if (lc < 1) lc = 1;
-    }
-    return lc;
 }
 
 template <typename T, int D, bool NT>
@@ -347,17 +325,12 @@ int launch_gp_batch(pgps_ctx* ctx, int B, GpBatchArgs<T> b) {
         b.nlanes = (long)b.nblocks * kBlock;
         if (b.nblocks > 65535 * 16) return PGPS_E_INVALID;
         const size_t nb = (size_t)b.nblocks, nl = (size_t)b.nlanes, nB = (size_t)B;
-        auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-        size_t off = 0;
-        const size_t o_spine = off; off = up(off + nB * nb * Dim<D>::NFILT * sizeof(T));
-        const size_t o_lpre = off;  off = up(off + nB * nl * Dim<D>::NFILT * sizeof(T));
-        const size_t o_ll = off;    off = up(off + nB * nb * sizeof(double));
-        int rc = ensure(ctx, ctx->ws, off);
-        if (rc) return rc;
-        char* base = (char*)ctx->ws.p;
-        b.spine = (T*)(base + o_spine);
-        b.lpre = (T*)(base + o_lpre);
-        b.llpart = (double*)(base + o_ll);
+        Carver c(256);
+        const auto spine = c.part<T>(nB * nb * Dim<D>::NFILT), lpre = c.part<T>(nB * nl * Dim<D>::NFILT);
+        const auto llpart = c.part<double>(nB * nb);
+        Scratch s;
+        if (int rc = commit(ctx, ctx->ws, c, &s)) return rc;
+        b.spine = s(spine); b.lpre = s(lpre); b.llpart = s(llpart);
         const dim3 grid(b.nblocks, B), block(kBlock);
         timed_launch(ctx, PGPS_K_FILTER_REDUCE, k_gpb_reduce<T, D>, grid, block, 0, b);
         timed_launch(ctx, PGPS_K_FILTER_APPLY, k_gpb_apply<T, D>, grid, block, 0, b);
@@ -392,33 +365,29 @@ int launch_gp_predict_batch(pgps_ctx* ctx, int B, GpBatchArgs<T> b) {
         b.nblocks = one ? 1 : (int)((b.N + (long)kBlock * lc - 1) / ((long)kBlock * lc));
         b.nlanes = (long)b.nblocks * kBlock;
         if (b.nblocks > 65535) return PGPS_E_INVALID;    // (6.7e7 merged steps at 4 per lane: one model's scratch would be 10 GB)
-        // scratch of ONE model, every part a multiple of 256 bytes
+        // The slices of a kind lie side by side (gp_batch_select strides them by the UNROUNDED record counts for the scan
+        // records, as launch_gp_batch does, and by bs_fm / bs_fP for the moments: a model's slice of those is rounded to 256
+        // bytes).  The layout of ONE model is what a model costs the budget
         const size_t nb = (size_t)b.nblocks, nl = (size_t)b.nlanes, n = (size_t)b.N;
-        auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-        const size_t s_spine = up(nb * Dim<D>::NFILT * sizeof(T)), s_lpre = up(nl * Dim<D>::NFILT * sizeof(T));
-        const size_t s_sspine = up(nb * Dim<D>::NSMTH * sizeof(T)), s_lsuf = up(nl * Dim<D>::NSMTH * sizeof(T));
-        const size_t s_ll = up(nb * sizeof(double)), s_fm = up(n * D * sizeof(T)), s_fP = up(n * D * D * sizeof(T));
-        const size_t per_model = s_spine + s_lpre + s_sspine + s_lsuf + s_ll + s_fm + s_fP;
-        const size_t budget = ctx->batch_scratch ? ctx->batch_scratch : kBatchScratchDefault;
-        size_t group = budget / per_model;
-        if (group < 1) group = 1;                       // (one model is the least a launch can hold)
-        if (group > (size_t)B) group = (size_t)B;
-        if (group > 65535) group = 65535;               // grid.y
-        int rc = ensure(ctx, ctx->ws, group * per_model);
-        if (rc) return rc;
-        // the slices of a kind lie side by side (gp_batch_select strides them by the UNROUNDED record counts for the scan
-        // records, as launch_gp_batch does, and by bs_fm / bs_fP for the moments)
-        char* base = (char*)ctx->ws.p;
-        size_t off = 0;
-        b.spine = (T*)(base + off);  off += up(group * nb * Dim<D>::NFILT * sizeof(T));
-        b.lpre = (T*)(base + off);   off += up(group * nl * Dim<D>::NFILT * sizeof(T));
-        b.sspine = (T*)(base + off); off += up(group * nb * Dim<D>::NSMTH * sizeof(T));
-        b.lsuf = (T*)(base + off);   off += up(group * nl * Dim<D>::NSMTH * sizeof(T));
-        b.llpart = (double*)(base + off); off += up(group * nb * sizeof(double));
-        b.fms = (T*)(base + off);    off += group * s_fm;
-        b.fPs = (T*)(base + off);    off += group * s_fP;
-        b.bs_fm = (long)(s_fm / sizeof(T));
-        b.bs_fP = (long)(s_fP / sizeof(T));
+        b.bs_fm = (long)(align_up(n * D * sizeof(T), 256) / sizeof(T));
+        b.bs_fP = (long)(align_up(n * D * D * sizeof(T), 256) / sizeof(T));
+        struct Parts { Part<T> spine, lpre, sspine, lsuf, fms, fPs; Part<double> ll; };
+        auto lay = [&](Carver& c, size_t g) {
+            Parts p;
+            p.spine = c.part<T>(g * nb * Dim<D>::NFILT);  p.lpre = c.part<T>(g * nl * Dim<D>::NFILT);
+            p.sspine = c.part<T>(g * nb * Dim<D>::NSMTH); p.lsuf = c.part<T>(g * nl * Dim<D>::NSMTH);
+            p.ll = c.part<double>(g * nb);
+            p.fms = c.part<T>(g * (size_t)b.bs_fm);       p.fPs = c.part<T>(g * (size_t)b.bs_fP);
+            return p;
+        };
+        Carver c1(256), c(256);
+        lay(c1, 1);
+        const size_t group = batch_group(batch_budget_fused(ctx), 0, c1.bytes(), (size_t)B);
+        const Parts p = lay(c, group);
+        Scratch s;
+        if (int rc = commit(ctx, ctx->ws, c, &s)) return rc;
+        b.spine = s(p.spine); b.lpre = s(p.lpre); b.sspine = s(p.sspine); b.lsuf = s(p.lsuf);
+        b.llpart = s(p.ll); b.fms = s(p.fms); b.fPs = s(p.fPs);
         const double* models = b.models;
         T* pmean = b.pmean;
         T* pvar = b.pvar;
@@ -466,13 +435,15 @@ int launch_gp_adj(pgps_ctx* ctx, GpArgs<double> g, double* out) {
         int rc = carve_workspace<double, D>(ctx, a);
         if (rc) return rc;
         constexpr int NX = D + Dim<D>::SYM, NST = gp_adj_nstat<D>();
-        const size_t n_xs = (size_t)a.Lc * NX * (size_t)a.nlanes, n_gp = (size_t)a.nblocks * NST;
-        rc = ensure(ctx, ctx->gadj, (n_xs + n_gp) * sizeof(double));
-        if (rc) return rc;
+        // the kept states and the workgroup partials, packed (the states are a whole number of 256-lane rows)
+        Carver cg(sizeof(double));
+        const auto xs = cg.part<double>((size_t)a.Lc * NX * (size_t)a.nlanes), gpart = cg.part<double>((size_t)a.nblocks * NST);
+        Scratch sg;
+        if ((rc = commit(ctx, ctx->gadj, cg, &sg))) return rc;
         GpAdjArgs ga{};
         ga.g = g;
-        ga.xs = (double*)ctx->gadj.p;
-        ga.gpart = ga.xs + n_xs;
+        ga.xs = sg(xs);
+        ga.gpart = sg(gpart);
         ga.out = out;
         const dim3 grid(a.nblocks), block(kBlock);
         if (one) {
@@ -510,34 +481,32 @@ int launch_gp_adj_batch(pgps_ctx* ctx, int B, GpBatchArgs<double> b, double* out
         b.nlanes = (long)b.nblocks * kBlock;
         if (b.nblocks > 65535) return PGPS_E_INVALID;
         constexpr int NX = D + Dim<D>::SYM, NST = gp_adj_nstat<D>();
-        // scratch of ONE model: the scan records in ctx->ws, the kept states and the workgroup partials in ctx->gadj
+        // The scan records in ctx->ws, the kept states and the workgroup partials in ctx->gadj; the slices of a kind lie side by
+        // side, strided by the unrounded record counts (gp_batch_select, gp_adj_batch_select) -- the kept states by a model's
+        // count rounded to 256 bytes.  The two layouts of ONE model are what a model costs the budget
         const size_t nb = (size_t)b.nblocks, nl = (size_t)b.nlanes;
-        auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-        const size_t s_xs = up((size_t)lc * NX * nl * sizeof(double));
-        const size_t per_ws = up(nb * Dim<D>::NFILT * 8) + up(nl * Dim<D>::NFILT * 8) + up(nb * Dim<D>::NSMTH * 8) +
-                              up(nl * Dim<D>::NSMTH * 8) + up(nb * 8);
-        const size_t per_gadj = s_xs + up(nb * NST * 8);
-        const size_t budget = ctx->batch_scratch ? ctx->batch_scratch : kBatchScratchDefault;
-        size_t group = budget / (per_ws + per_gadj);
-        if (group < 1) group = 1;                       // (one model is the least a launch can hold)
-        if (group > (size_t)B) group = (size_t)B;
-        if (group > 65535) group = 65535;               // grid.y
-        int rc = ensure(ctx, ctx->ws, group * per_ws);
-        if (rc) return rc;
-        rc = ensure(ctx, ctx->gadj, group * per_gadj);
-        if (rc) return rc;
-        // the slices of a kind lie side by side, strided by the unrounded record counts (gp_batch_select, gp_adj_batch_select)
-        char* base = (char*)ctx->ws.p;
-        size_t off = 0;
-        b.spine = (double*)(base + off);  off += up(group * nb * Dim<D>::NFILT * 8);
-        b.lpre = (double*)(base + off);   off += up(group * nl * Dim<D>::NFILT * 8);
-        b.sspine = (double*)(base + off); off += up(group * nb * Dim<D>::NSMTH * 8);
-        b.lsuf = (double*)(base + off);   off += up(group * nl * Dim<D>::NSMTH * 8);
-        b.llpart = (double*)(base + off);
+        const size_t bs_xs = align_up((size_t)lc * NX * nl * sizeof(double), 256) / sizeof(double);
+        struct Parts { Part<double> spine, lpre, sspine, lsuf, ll, xs, gpart; };
+        auto lay = [&](Carver& cw, Carver& cg, size_t g) {
+            Parts p;
+            p.spine = cw.part<double>(g * nb * Dim<D>::NFILT);  p.lpre = cw.part<double>(g * nl * Dim<D>::NFILT);
+            p.sspine = cw.part<double>(g * nb * Dim<D>::NSMTH); p.lsuf = cw.part<double>(g * nl * Dim<D>::NSMTH);
+            p.ll = cw.part<double>(g * nb);
+            p.xs = cg.part<double>(g * bs_xs);                  p.gpart = cg.part<double>(g * nb * NST);
+            return p;
+        };
+        Carver cw1(256), cg1(256), cw(256), cg(256);
+        lay(cw1, cg1, 1);
+        const size_t group = batch_group(batch_budget_fused(ctx), 0, cw1.bytes() + cg1.bytes(), (size_t)B);
+        const Parts p = lay(cw, cg, group);
+        Scratch s, sg;
+        if (int rc = commit(ctx, ctx->ws, cw, &s)) return rc;
+        if (int rc = commit(ctx, ctx->gadj, cg, &sg)) return rc;
+        b.spine = s(p.spine); b.lpre = s(p.lpre); b.sspine = s(p.sspine); b.lsuf = s(p.lsuf); b.llpart = s(p.ll);
         GpAdjBatchArgs ab{};
-        ab.xs = (double*)ctx->gadj.p;
-        ab.bs_xs = (long)(s_xs / sizeof(double));
-        ab.gpart = ab.xs + group * (size_t)ab.bs_xs;
+        ab.xs = sg(p.xs);
+        ab.bs_xs = (long)bs_xs;
+        ab.gpart = sg(p.gpart);
         const double* models = b.models;
         const dim3 block(kBlock);
         for (size_t g0 = 0; g0 < (size_t)B; g0 += group) {

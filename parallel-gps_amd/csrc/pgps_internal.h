@@ -26,7 +26,7 @@ struct pgps_ctx {
     int single_pass = -1;               // single-pass filter kernel: -1 = auto, 0 = off, 1 = on
     int lookback_window = 256;          // tiles per look-back window (<= 256; small values are for tests)
     int block = 0;                      // lane-chunk workgroups: 0 = auto, 128 / 256 lanes (pgps_set_block)
-    size_t batch_scratch = 0;           // batched predict: scratch budget in bytes, 0 = kBatchScratchDefault (pgps_set_batch_scratch)
+    size_t batch_scratch = 0;           // batched predict: scratch budget in bytes, 0 = the family's default (pgps_scratch.h; pgps_set_batch_scratch)
     int batch_form = 0;                 // batched fused predict: 0 = automatic, 1 = one workgroup per model, 2 = three launches (pgps_set_batch_form)
     int one_launch = -1;                // fused (pgps_gp_*) calls of short series in ONE launch: -1 = auto (N <= kOneLaunchAuto), 0 = never, n > 0 = up to n steps
     long grad_pack = -1;                // gradient at d <= 2: one direction per model up to this many steps (-1 = automatic, 0 = never)
@@ -296,10 +296,6 @@ int launch_gp_predict_batch(pgps_ctx* ctx, int B, GpBatchArgs<T> b);
 // that fit the context's batch budget (T names the unit that holds the instantiation: call it with T = double)
 template <typename T, int D>
 int launch_gp_adj_batch(pgps_ctx* ctx, int B, GpBatchArgs<double> b, double* out);
-// scratch budget of the batched fused predict when pgps_set_batch_scratch has not set one: the smallest budget beyond which
-// the measured time per model no longer improves (B = 1000, N + K = 5000, d = 2: 3.79, 2.83, 2.35, 2.19 ms at 8, 16, 32, 64 MiB,
-// 2.2 .. 2.7 ms at 256 MiB and 1 GiB)
-constexpr size_t kBatchScratchDefault = 64u << 20;
 // form 1 of the batched fused predict (one workgroup per model, pgps_set_batch_form(ctx, 1)) is taken up to this many merged steps
 constexpr long kBatchOneMax = 65536;
 
@@ -328,6 +324,9 @@ struct GpMultiArgs {
     double* pmean;              // (K, M)
     double* pvar;               // (K,)
 };
+// steps per lane of the batched fused launches, and the geometry of both multi-output launches by it (pgps_ctx.hip)
+int batch_steps_per_lane(const pgps_ctx* ctx, int B, long N);
+void multi_geometry(const pgps_ctx* ctx, long N, int groups_all, int* Lc, int* nblocks);
 // ll (M,) [device] or null; predict != 0: a.rows, a.qslot, a.pmean, a.pvar set.  Picks the geometry once per call from
 // (M, N), carves the scratch and runs the column groups in rounds that fit the context's batch budget
 template <int D>

@@ -3,6 +3,7 @@
 // covariance share.  The kernels are the row-, wave-cooperative and two-rows units'.
 #include "pgps_host.h"
 #include "pgps_gradlti.h"
+#include "pgps_scratch.h"
 
 using namespace pgps;
 
@@ -453,10 +454,6 @@ extern "C" int pgps_lti_predict_dev_f64(pgps_ctx* c, long N, long K, int d, cons
 // query grid.  ONE merge, one batched discretisation, then the row-cooperative filter + smoother + projection of all
 // models of a group side by side (blockIdx.y = model: model_view, pgps_rc.hip.h) -- the launches of ONE predict, whatever B.
 // ---------------------------------------------------------------------------------------------
-// default budget of the general-LTI batch (a model is ~3 (N + K) d^2 doubles, 12.6 MB at d = 11, N + K = 4216): d = 11, B = 64
-// measured 34.7, 23.4, 16.6, 13.6, 12.6 ms at 8, 32, 64, 256 MiB and 1 GiB -- still improving at the largest budget measured,
-// where the whole batch is one group
-constexpr size_t kBatchScratchDefaultLti = (size_t)1 << 30;
 int pgps::lti_predict_batch_merged(pgps_ctx* ctx, int B, size_t m, long K, int d, const double* models, const double* ts_m,
                                     const double* ys_m, double t0, const int* qslot, double* mean, double* var, double* ll) {
     const size_t dd = (size_t)d * d, ms = 2 * dd + d + 1;
@@ -464,12 +461,7 @@ int pgps::lti_predict_batch_merged(pgps_ctx* ctx, int B, size_t m, long K, int d
         if (!(models[(size_t)b * ms + ms - 1] > 0.0)) return PGPS_E_INVALID;
     // per model: Fs, the stored smoothing elements E (as much again) and g, plus L and the chain records inside the scan's
     // own workspace -- about 3 m d^2 doubles; the models run in groups that fit the context's batch budget
-    const size_t per_model = (3 * m * dd + m * d) * sizeof(double);
-    const size_t budget = ctx->batch_scratch ? ctx->batch_scratch : kBatchScratchDefaultLti;
-    size_t group = budget / per_model;
-    if (group < 1) group = 1;
-    if (group > (size_t)B) group = (size_t)B;
-    if (group > 65535) group = 65535;                   // grid.y
+    const size_t group = batch_group(batch_budget_lti(ctx), 0, (3 * m * dd + m * d) * sizeof(double), (size_t)B);
     double *table, *Fs, *Es, *gs;
     TRY(stage_in<double>(ctx, ctx->lti[0], models, (size_t)B * ms, &table));
     TRY(stage_in<double>(ctx, ctx->lti[4], nullptr, group * m * dd, &Fs));

@@ -2,6 +2,7 @@
 // pgps_multi_grad.hip.h (and k_gpm_reduce at their tile width) instantiated for PGPS_MULTI_D, and the launch function the
 // C ABI dispatches to.
 #include "pgps_multi_grad.hip.h"
+#include "pgps_scratch.h"
 
 #ifndef PGPS_MULTI_D
 #error "compile with -DPGPS_MULTI_D=<1|2|3>"
@@ -16,46 +17,28 @@ int launch_gp_multi_grad(pgps_ctx* ctx, GpMultiArgs a, double* out) {
     using SE = SmthElemM<double, D, MC>;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int groups_all = (a.M + MC - 1) / MC;
-    // geometry ONCE per call from (M, N), by the rule of launch_gp_multi: neither a column's log-likelihood nor the sums
-    // depend on the round a group runs in
-    int lc = ctx->chunk;
-    if (lc <= 0) {
-        lc = 16;
-        while (lc > 4 && (long)groups_all * ((a.N + (long)kBlock * lc - 1) / ((long)kBlock * lc)) < 1024) lc /= 2;
-        if (a.N < (long)kBlock * 4) lc = (int)((a.N + kBlock - 1) / kBlock);
-        if (lc < 1) lc = 1;
-    }
-    a.Lc = lc;
-    a.nblocks = (int)((a.N + (long)kBlock * lc - 1) / ((long)kBlock * lc));
+    multi_geometry(ctx, a.N, groups_all, &a.Lc, &a.nblocks);
     a.nlanes = (long)a.nblocks * kBlock;
     if (a.nblocks > 0x7fffff) return PGPS_E_INVALID;
     a.rows = nullptr;
     const size_t nb = (size_t)a.nblocks, nl = (size_t)a.nlanes;
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    // scratch of ONE group, and what the groups of the whole call share
-    const size_t g_spine = nb * FE::N * 8, g_lpre = nl * FE::N * 8, g_sspine = nb * SE::N * 8, g_lsuf = nl * SE::N * 8;
-    const size_t g_xs = nl * (size_t)lc * NX * 8;
-    const size_t per_group = g_spine + g_lpre + g_sspine + g_lsuf + g_xs;
-    const size_t s_ll = up((size_t)groups_all * MC * nb * 8), s_gp = up((size_t)groups_all * nb * NST * 8);
-    const size_t budget = ctx->batch_scratch ? ctx->batch_scratch : kBatchScratchDefault;
-    size_t group = budget > s_ll + s_gp ? (budget - s_ll - s_gp) / per_group : 0;
-    if (group < 1) group = 1;                           // (one group is the least a launch can hold)
-    if (group > (size_t)groups_all) group = (size_t)groups_all;
-    if (group > 65535) group = 65535;                   // grid.y
-    int rc = ensure(ctx, ctx->ws, s_ll + s_gp + up(group * g_spine) + up(group * g_lpre) + up(group * g_sspine) +
-                                      up(group * g_lsuf) + up(group * g_xs));
-    if (rc) return rc;
-    char* base = (char*)ctx->ws.p;
-    size_t off = 0;
+    // doubles of ONE group; what the groups of the whole call share comes first
+    const size_t g_spine = nb * FE::N, g_lpre = nl * FE::N, g_sspine = nb * SE::N, g_lsuf = nl * SE::N;
+    const size_t g_xs = nl * (size_t)a.Lc * NX;
+    Carver c(256);
+    const auto llpart = c.part<double>((size_t)groups_all * MC * nb), gpart = c.part<double>((size_t)groups_all * nb * NST);
+    const size_t group = batch_group(batch_budget_fused(ctx), c.bytes(), (g_spine + g_lpre + g_sspine + g_lsuf + g_xs) * sizeof(double),
+                                     (size_t)groups_all);
+    const auto spine = c.part<double>(group * g_spine), lpre = c.part<double>(group * g_lpre);
+    const auto sspine = c.part<double>(group * g_sspine), lsuf = c.part<double>(group * g_lsuf);
+    const auto xs = c.part<double>(group * g_xs);
+    Scratch s;
+    if (int rc = commit(ctx, ctx->ws, c, &s)) return rc;
     GpMultiGradArgs ga{};
-    a.llpart = (double*)(base + off); off += s_ll;
-    ga.gpart = (double*)(base + off); off += s_gp;
-    a.spine = (double*)(base + off);  off += up(group * g_spine);
-    a.lpre = (double*)(base + off);   off += up(group * g_lpre);
-    a.sspine = (double*)(base + off); off += up(group * g_sspine);
-    a.lsuf = (double*)(base + off);   off += up(group * g_lsuf);
-    ga.xs = (double*)(base + off);
-    ga.gs_xs = (long)(g_xs / 8);
+    a.llpart = s(llpart); ga.gpart = s(gpart);
+    a.spine = s(spine); a.lpre = s(lpre); a.sspine = s(sspine); a.lsuf = s(lsuf);
+    ga.xs = s(xs);
+    ga.gs_xs = (long)g_xs;
     const dim3 block(kBlock);
     for (size_t g0 = 0; g0 < (size_t)groups_all; g0 += group) {
         const unsigned G = (unsigned)((size_t)groups_all - g0 < group ? (size_t)groups_all - g0 : group);

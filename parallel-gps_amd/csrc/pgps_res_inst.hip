@@ -1,6 +1,7 @@
 // pgps_res_inst.hip -- the resident filter + smoother launch (pgps_resident.hip.h) instantiated for one (dtype, d):
 // array form (Fs, Qs given: pgps_pkfs_dev_*) and fused form (Matern model + time stamps: pgps_gp_dev_*).
 #include "pgps_resident.hip.h"
+#include "pgps_scratch.h"
 
 #ifndef PGPS_RES_T
 #error "compile with -DPGPS_RES_T=<float|double> -DPGPS_RES_D=<d>"
@@ -26,18 +27,16 @@ int launch_resident(pgps_ctx* ctx, ResArgs<T> ra, bool fused, bool smooth) {
     a.seg_first = 1;
     a.seg_last = 1;
     a.shortcut = ctx->shortcut != 0 ? 1 : 0;        // (a workgroup spans 2048 or 4096 steps; the test is on the data either way)
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t nb = (size_t)a.nblocks;
     // the workspace holds the log-likelihood partials alone: the totals travel as tagged granules in the context's own arrays
     // (which never move or grow: a granule of an earlier launch keeps its tag, wherever the workspace has gone since)
-    const size_t off = up(nb * sizeof(double));
-    int rc = ensure(ctx, ctx->ws, off);
-    if (rc) return rc;
-    ctx->ws_epoch++;
-    char* base = (char*)ctx->ws.p;
+    const size_t nb = (size_t)a.nblocks;
+    Carver c(256);
+    const auto llpart = c.part<double>(nb);
+    Scratch s;
+    if (int rc = commit(ctx, ctx->ws, c, &s)) return rc;
     a.spine = nullptr;
     a.sspine = nullptr;
-    a.llpart = (double*)base;
+    a.llpart = s(llpart);
     a.status = ctx->status_word;
     const unsigned e = ctx->res_epoch++;
     ra.bar = ctx->status_word + kResBarWord + (e & 1u) * kResBarSet;
@@ -54,8 +53,7 @@ int launch_resident(pgps_ctx* ctx, ResArgs<T> ra, bool fused, bool smooth) {
     const bool skew = ctx->res_delay_tile >= 0;        // the start-skew hook (pgps_debug_resident_delay): diagnostics only
     if (ctx->resident == 2 || skew) {
         // (nblocks, 16) workgroup stamps, then (nblocks, 8) per-wave stamps (pgps_resident_wave_stamps)
-        rc = ensure(ctx, ctx->res_stamps, nb * (16 + 8) * sizeof(long long));
-        if (rc) return rc;
+        if (int rc = ensure(ctx, ctx->res_stamps, nb * (16 + 8) * sizeof(long long))) return rc;
         if (ctx->resident == 2) ra.stamps = (long long*)ctx->res_stamps.p;
         ctx->res_stamp_blocks = a.nblocks;
     }
@@ -63,7 +61,7 @@ int launch_resident(pgps_ctx* ctx, ResArgs<T> ra, bool fused, bool smooth) {
         // every record a workgroup could read before it is published is NaN: a stale read cannot match by luck (the granules'
         // data words all ones, which is a NaN in either half of a double, under a tag of all ones, which is no epoch)
         HIPCHK(ctx, hipMemsetAsync(ctx->res_stamps.p, 0, nb * 16 * sizeof(long long), ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(base, 0xFF, off, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(a.llpart, 0xFF, c.bytes(), ctx->stream));
         HIPCHK(ctx, hipMemsetAsync(ctx->res_gran, 0xFF, kResGranBytes, ctx->stream));
         ra.wstamps = (long long*)ctx->res_stamps.p;
         ra.delay_tile = ctx->res_delay_tile;

@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "pgps_sample.hip.h"
+#include "pgps_scratch.h"
 
 #ifndef PGPS_SAMP_T
 #error "compile with -DPGPS_SAMP_T=<float|double> -DPGPS_SAMP_D=<d>"
@@ -20,11 +21,12 @@ int launch_sample(pgps_ctx* ctx, SampleArgs<T> a) {
     const long groups = ((long)a.S + SG - 1) / SG;
     if (groups > 65535) return PGPS_E_INVALID;
     a.ngroups = (int)groups;
-    const size_t lsuf = (size_t)a.ngroups * NREC * (size_t)a.nlanes, spine = (size_t)a.ngroups * a.nblocks * NREC;
-    int rc = ensure(ctx, ctx->smp, (lsuf + spine) * sizeof(T) + 256);
-    if (rc) return rc;
-    a.lsuf = (T*)ctx->smp.p;
-    a.spine = a.lsuf + (lsuf + 31) / 32 * 32;
+    // the spine starts on a whole 32 elements behind the lane suffixes (those are whole 256-lane rows)
+    Carver c(32 * sizeof(T));
+    const auto lsuf = c.part<T>((size_t)a.ngroups * NREC * (size_t)a.nlanes), spine = c.part<T>((size_t)a.ngroups * a.nblocks * NREC);
+    Scratch s;
+    if (int rc = commit(ctx, ctx->smp, c, &s)) return rc;
+    a.lsuf = s(lsuf); a.spine = s(spine);
     const dim3 grid(a.nblocks, a.ngroups), block(kBlock);
     hipLaunchKernelGGL((k_sample_reduce<T, D>), grid, block, 0, ctx->stream, a);
     hipLaunchKernelGGL((k_sample_apply<T, D>), grid, block, 0, ctx->stream, a);

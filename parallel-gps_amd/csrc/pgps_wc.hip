@@ -32,6 +32,7 @@
 #include "pgps_math.h"
 #include "pgps_wc_args.h"
 #include "pgps_gradlti.h"
+#include "pgps_scratch.h"
 
 namespace pgps {
 namespace wc {
@@ -1785,8 +1786,6 @@ static __global__ __launch_bounds__(256) void seg_unpack_s(int d, const Real* ga
 }  // namespace rc
 
 // ---- host side ----------------------------------------------------------------------------------------
-static inline size_t wc_align(size_t x) { return (x + 255) / 256 * 256; }
-
 // one segment of a sharded series (pgps_seg_*): the records exchanged between the ranks and the scratch of the stitching
 template <typename T>
 struct WcSeg {
@@ -2093,45 +2092,33 @@ static int launch_scan_wc_impl(pgps_ctx* ctx, ScanArgs<T> sa, int d, Mode mode, 
     a.seg_first = seg ? (sa.rank == 0) : 1;
     a.seg_last = seg ? (sa.rank == sa.nranks - 1) : 1;
     const size_t dd = (size_t)d * d, nf = nfilt(d), ns = nsmth(d), nc = (size_t)a.nchunk, ng = (size_t)a.ngroup;
-    size_t off = 0;
-    const size_t o_agg1 = off;   off = wc_align(off + nc * nf * sizeof(T));
-    const size_t o_lpre1 = off;  off = wc_align(off + nc * nf * sizeof(T));
-    const size_t o_agg2 = off;   off = wc_align(off + ng * nf * sizeof(T));
-    const size_t o_carry2 = off; off = wc_align(off + ng * (d + dd) * sizeof(T));
-    const size_t o_sagg1 = off;  off = wc_align(off + nc * ns * sizeof(T));
-    const size_t o_lsuf1 = off;  off = wc_align(off + nc * ns * sizeof(T));
-    const size_t o_sagg2 = off;  off = wc_align(off + ng * ns * sizeof(T));
-    const size_t o_sc2 = off;    off = wc_align(off + ng * (d + dd) * sizeof(T));
-    const size_t o_ll = off;     off = wc_align(off + nc * sizeof(double));
-    const size_t o_ksA = off;    off = wc_align(off + ng * nf * sizeof(T));
-    const size_t o_ksB = off;    off = wc_align(off + ng * nf * sizeof(T));
-    // segments: the same layout in all three phases (the workspace must not move between them)
-    const size_t nr = seg ? (size_t)sa.nranks : 0;
-    const size_t o_totf = off;   off = wc_align(off + nr * nf * sizeof(T));
-    const size_t o_tots = off;   off = wc_align(off + nr * ns * sizeof(T));
-    const size_t o_cin = off;    if (seg) off = wc_align(off + (d + dd) * sizeof(T));
-    const size_t o_cback = off;  if (seg) off = wc_align(off + (d + dd) * sizeof(T));
-    const size_t o_halo = off;   if (seg) off = wc_align(off + 2 * dd * sizeof(T));
-    const size_t o_E = off;      if (seg) off = wc_align(off + (size_t)sa.N * dd * sizeof(T));
-    const size_t o_en = off;     off = wc_align(off + nc * (d + dd) * sizeof(T));
-    const size_t o_sen = off;    off = wc_align(off + nc * (d + dd) * sizeof(T));
-    const size_t o_gp = off;     if (gr) off = wc_align(off + nc * (size_t)grad_lti_nstat(d) * sizeof(double));
-    int rc = ensure(ctx, ctx->ws, off);
-    if (rc) return rc;
-    char* base = (char*)ctx->ws.p;
-    if (gr) gr->gpart = (double*)(base + o_gp);
-    a.agg1 = (T*)(base + o_agg1); a.lpre1 = (T*)(base + o_lpre1); a.agg2 = (T*)(base + o_agg2);
-    a.carry2 = (T*)(base + o_carry2); a.sagg1 = (T*)(base + o_sagg1); a.lsuf1 = (T*)(base + o_lsuf1);
-    a.sagg2 = (T*)(base + o_sagg2); a.scarry2 = (T*)(base + o_sc2); a.llpart = (double*)(base + o_ll);
-    a.Es = seg ? (T*)(base + o_E) : a.sPs;
-    a.enter1 = (T*)(base + o_en); a.senter1 = (T*)(base + o_sen);
-    a.ksA = (T*)(base + o_ksA); a.ksB = (T*)(base + o_ksB);
+    Carver c(256);
+    const auto agg1 = c.part<T>(nc * nf), lpre1 = c.part<T>(nc * nf), agg2 = c.part<T>(ng * nf), carry2 = c.part<T>(ng * (d + dd));
+    const auto sagg1 = c.part<T>(nc * ns), lsuf1 = c.part<T>(nc * ns), sagg2 = c.part<T>(ng * ns), sc2 = c.part<T>(ng * (d + dd));
+    const auto llpart = c.part<double>(nc);
+    const auto ksA = c.part<T>(ng * nf), ksB = c.part<T>(ng * nf);
+    // segments: the same layout in all three phases (the workspace must not move between them); nothing of it otherwise
+    const size_t nr = seg ? (size_t)sa.nranks : 0, sg1 = seg ? 1 : 0;
+    const auto totf = c.part<T>(nr * nf), tots = c.part<T>(nr * ns);
+    const auto cin = c.part<T>(sg1 * (d + dd)), cback = c.part<T>(sg1 * (d + dd)), halo = c.part<T>(sg1 * 2 * dd);
+    const auto Es = c.part<T>(sg1 * (size_t)sa.N * dd);
+    const auto en = c.part<T>(nc * (d + dd)), sen = c.part<T>(nc * (d + dd));
+    const auto gpart = c.part<double>(gr ? nc * (size_t)grad_lti_nstat(d) : 0);
+    Scratch s;
+    if (int rc = commit(ctx, ctx->ws, c, &s)) return rc;
+    if (gr) gr->gpart = s(gpart);
+    a.agg1 = s(agg1); a.lpre1 = s(lpre1); a.agg2 = s(agg2);
+    a.carry2 = s(carry2); a.sagg1 = s(sagg1); a.lsuf1 = s(lsuf1);
+    a.sagg2 = s(sagg2); a.scarry2 = s(sc2); a.llpart = s(llpart);
+    a.Es = seg ? s(Es) : a.sPs;
+    a.enter1 = s(en); a.senter1 = s(sen);
+    a.ksA = s(ksA); a.ksB = s(ksB);
     WcSeg<T> sgv{};
     if (seg) {
         sgv.rank = sa.rank; sgv.nranks = sa.nranks;
         sgv.rec_f = sa.rec_f; sgv.gathered_f = sa.gathered_f; sgv.rec_s = sa.rec_s; sgv.gathered_s = sa.gathered_s;
-        sgv.tot_f = (T*)(base + o_totf); sgv.tot_s = (T*)(base + o_tots);
-        sgv.carry_in = (T*)(base + o_cin); sgv.carry_back = (T*)(base + o_cback); sgv.halo = (T*)(base + o_halo);
+        sgv.tot_f = s(totf); sgv.tot_s = s(tots);
+        sgv.carry_in = s(cin); sgv.carry_back = s(cback); sgv.halo = s(halo);
         sgv.ll = sa.ll;
     }
     const WcSeg<T>* sg = seg ? &sgv : nullptr;
@@ -2446,8 +2433,6 @@ int launch_disc_rc(pgps_ctx* ctx, long N, int d, const double* F, const double* 
     return PGPS_E_UNSUPPORTED_DIM;
 }
 
-static inline size_t rc_align(size_t x) { return (x + 255) / 256 * 256; }
-
 // Steps per chain of the batched row-cooperative calls (log-likelihood, predict, gradient), B models over N steps: the
 // models multiply the chains, keep about 8192 in flight; at most 128 steps, at least 8.  One statement for all of them:
 // a row of a batch must not depend on which call, or which group of a call, it runs in.
@@ -2569,32 +2554,27 @@ static int scan_rc_entry(pgps_ctx* ctx, ScanArgs<Real> sa, int d, Mode mode, int
         a.Rs = sa.carry_in;
         if (mode == MODE_PKFS) { a.bs_sagg = (long)(nc * ns); a.bs_g = (long)sa.N * d; a.bs_out = bs_out; }
     }
-    size_t off = 0;
-    const size_t o_aggA = off;  off = rc_align(off + nbm * nc * nf * sizeof(Real));
-    const size_t o_aggB = off;  off = rc_align(off + nbm * nc * nf * sizeof(Real));
-    const size_t o_sagA = off;  off = rc_align(off + nbm * nc * ns * sizeof(Real));
-    const size_t o_sagB = off;  off = rc_align(off + nbm * nc * ns * sizeof(Real));
-    const size_t o_ll = off;    off = rc_align(off + nbm * nc * sizeof(double));
-    const size_t o_cf = off;    off = rc_align(off + nf * sizeof(Real));
-    const size_t o_cs = off;    off = rc_align(off + ns * sizeof(Real));
-    const size_t o_L = off;     if (mode != MODE_PKF) off = rc_align(off + nbm * (size_t)sa.N * dd * sizeof(Real));
+    Carver c(256);
+    const auto p_aggA = c.part<Real>(nbm * nc * nf), p_aggB = c.part<Real>(nbm * nc * nf);
+    const auto p_sagA = c.part<Real>(nbm * nc * ns), p_sagB = c.part<Real>(nbm * nc * ns);
+    const auto p_ll = c.part<double>(nbm * nc);
+    const auto p_cf = c.part<Real>(nf), p_cs = c.part<Real>(ns);
+    const auto p_L = c.part<Real>(mode != MODE_PKF ? nbm * (size_t)sa.N * dd : 0);
     // segments: the smoothing elements wait in scratch until the smoother phase brings sms / sPs
-    const size_t o_E = off;     if (seg) off = rc_align(off + (size_t)sa.N * dd * sizeof(Real));
-    const size_t o_g = off;     if (seg) off = rc_align(off + (size_t)sa.N * d * sizeof(Real));
-    int rcode = ensure(ctx, ctx->ws, off);
-    if (rcode) return rcode;
-    char* base = (char*)ctx->ws.p;
-    a.llpart = (double*)(base + o_ll);
-    a.Lws = (Real*)(base + o_L);
-    a.Es = seg ? (Real*)(base + o_E) : a.sPs;
-    a.gs = seg ? (Real*)(base + o_g) : a.sms;
-    Real* aggA = (Real*)(base + o_aggA); Real* aggB = (Real*)(base + o_aggB);
-    Real* sagA = (Real*)(base + o_sagA); Real* sagB = (Real*)(base + o_sagB);
+    const auto p_E = c.part<Real>(seg ? (size_t)sa.N * dd : 0), p_g = c.part<Real>(seg ? (size_t)sa.N * d : 0);
+    Scratch s;
+    if (int rcode = commit(ctx, ctx->ws, c, &s)) return rcode;
+    a.llpart = s(p_ll);
+    a.Lws = s(p_L);
+    a.Es = seg ? s(p_E) : a.sPs;
+    a.gs = seg ? s(p_g) : a.sms;
+    Real* aggA = s(p_aggA); Real* aggB = s(p_aggB);
+    Real* sagA = s(p_sagA); Real* sagB = s(p_sagB);
     if (seg) {
         rc::SegInfo<Real> sg{};
         sg.rank = sa.rank; sg.nranks = sa.nranks;
         sg.rec_f = sa.rec_f; sg.gathered_f = sa.gathered_f; sg.rec_s = sa.rec_s; sg.gathered_s = sa.gathered_s;
-        sg.carry_rec = (Real*)(base + o_cf); sg.cb_rec = (Real*)(base + o_cs);
+        sg.carry_rec = s(p_cf); sg.cb_rec = s(p_cs);
         return rc::scan_rc_seg(ctx, d, a, mode, aggA, aggB, sagA, sagB, sg, sa.ll);
     }
     return rc::scan_rc(ctx, d, a, mode, aggA, aggB, sagA, sagB, sa.ll, geom_batch);
@@ -2606,6 +2586,16 @@ static int scan_rc_entry(pgps_ctx* ctx, ScanArgs<Real> sa, int d, Mode mode, int
 // kernels: the reverse sweep composes under the smoothing operator) -> backward pass (rc_gback1) -> finalize.
 // Everything is enqueued on the context's stream; `out` holds 1 + d d + 2 d + 1 doubles.
 // ====================================================================================================
+// the chains' records of both scans (two buffers each) and their partials, g models side by side
+struct GradLtiParts { Part<double> aggA, aggB, sagA, sagB, ll, gp; };
+static GradLtiParts grad_lti_lay(Carver& c, size_t g, size_t nc, size_t nf, size_t ns, size_t nst) {
+    GradLtiParts p;
+    p.aggA = c.part<double>(g * nc * nf); p.aggB = c.part<double>(g * nc * nf);
+    p.sagA = c.part<double>(g * nc * ns); p.sagB = c.part<double>(g * nc * ns);
+    p.ll = c.part<double>(g * nc);        p.gp = c.part<double>(g * nc * nst);
+    return p;
+}
+
 static int grad_level1_rc(pgps_ctx* ctx, int d, const GradLtiArgs& g, int phase) {
     switch (d) {
 #define PGPS_RC_CASE(DV) case DV: return rc::launch_rc_grad<DV>(ctx, g, phase);
@@ -2643,18 +2633,12 @@ int launch_ll_grad_lti(pgps_ctx* ctx, long N, int d, const double* model, double
     a.P0 = model + dd; a.H = model + 2 * dd; a.R = R; a.Fs = Fs; a.Qs = nullptr; a.ys = ys;
     a.seg_first = 1; a.seg_last = 1; a.implicit_q = 1; a.store_f = 0;
     const size_t nf = wc::nfilt(d), ns = wc::nsmth(d), nc = (size_t)a.nchunk, nst = (size_t)grad_lti_nstat(d);
-    size_t off = 0;
-    const size_t o_aggA = off;  off = rc_align(off + nc * nf * sizeof(double));
-    const size_t o_aggB = off;  off = rc_align(off + nc * nf * sizeof(double));
-    const size_t o_sagA = off;  off = rc_align(off + nc * ns * sizeof(double));
-    const size_t o_sagB = off;  off = rc_align(off + nc * ns * sizeof(double));
-    const size_t o_ll = off;    off = rc_align(off + nc * sizeof(double));
-    const size_t o_gp = off;    off = rc_align(off + nc * nst * sizeof(double));
-    if ((rcode = ensure(ctx, ctx->ws, off))) return rcode;
-    char* base = (char*)ctx->ws.p;
-    double *aggA = (double*)(base + o_aggA), *aggB = (double*)(base + o_aggB);
-    double *sagA = (double*)(base + o_sagA), *sagB = (double*)(base + o_sagB);
-    a.llpart = (double*)(base + o_ll);
+    Carver c(256);
+    const GradLtiParts p = grad_lti_lay(c, 1, nc, nf, ns, nst);
+    Scratch s;
+    if ((rcode = commit(ctx, ctx->ws, c, &s))) return rcode;
+    double *aggA = s(p.aggA), *aggB = s(p.aggB), *sagA = s(p.sagA), *sagB = s(p.sagB);
+    a.llpart = s(p.ll);
     a.agg1 = aggA;
     if ((rcode = rc::level1(ctx, d, a, 0))) return rcode;
     double* pre = aggA;
@@ -2663,7 +2647,7 @@ int launch_ll_grad_lti(pgps_ctx* ctx, long N, int d, const double* model, double
     g.N = N; g.d = d; g.Lw = a.Lw; g.nchunk = a.nchunk;
     g.Pinf = model + dd; g.H = model + 2 * dd; g.R = R; g.Fs = Fs; g.ys = ys; g.ts = ts; g.t0 = t0;
     g.fPs = (double*)ctx->lti[6].p; g.fms = (double*)ctx->lti[7].p;
-    g.pre = pre; g.sagg = sagA; g.llpart = a.llpart; g.gpart = (double*)(base + o_gp); g.out = out;
+    g.pre = pre; g.sagg = sagA; g.llpart = a.llpart; g.gpart = s(p.gp); g.out = out;
     if ((rcode = grad_level1_rc(ctx, d, g, 0))) return rcode;
     double* suf = sagA;
     if ((rcode = rc::ks_scan(ctx, d, 1, a.nchunk, sagA, sagB, &suf))) return rcode;
@@ -2679,8 +2663,6 @@ int launch_ll_grad_lti(pgps_ctx* ctx, long N, int d, const double* model, double
 // length is fixed HERE from (B, N), and both scans run as the whole call's do whatever the group, so a row depends
 // neither on its place in the table, nor on the other rows, nor on the groups the budget cuts the table into.
 // ====================================================================================================
-constexpr size_t kGradBatchScratchDefault = (size_t)1 << 30;        // as the general-LTI predict batch (pgps_lti_api.hip)
-
 int launch_ll_grad_lti_batch(pgps_ctx* ctx, long N, int d, int B, const double* table, long bs_model, const double* ts, double t0,
                              const double* ys, double* out) {
     RoctxRange range_("parallel_filter");
@@ -2696,30 +2678,18 @@ int launch_ll_grad_lti_batch(pgps_ctx* ctx, long N, int d, int B, const double* 
     }
     const long nchunk = (N + lw - 1) / lw;
     const size_t nf = wc::nfilt(d), ns = wc::nsmth(d), nc = (size_t)nchunk, nst = (size_t)grad_lti_nstat(d);
-    // per model: Fs and the kept filtered covariances (N d^2 each), the kept means, the chains' records of both scans (two
-    // buffers each) and their partials
-    const size_t per_ws = rc_align(nc * nf * 8) * 2 + rc_align(nc * ns * 8) * 2 + rc_align(nc * 8) + rc_align(nc * nst * 8);
-    const size_t per_model = (2 * n * dd + n * d) * sizeof(double) + per_ws;
-    const size_t budget = ctx->batch_scratch ? ctx->batch_scratch : kGradBatchScratchDefault;
-    size_t group = budget / per_model;
-    if (group < 1) group = 1;                           // (one model is the least a launch can hold)
-    if (group > (size_t)B) group = (size_t)B;
-    if (group > 65535) group = 65535;                   // grid.y
+    // per model: Fs and the kept filtered covariances (N d^2 each), the kept means, and its chains' records in the workspace
+    Carver c1(256), c(256);
+    grad_lti_lay(c1, 1, nc, nf, ns, nst);
+    const size_t group = batch_group(batch_budget_lti(ctx), 0, (2 * n * dd + n * d) * sizeof(double) + c1.bytes(), (size_t)B);
     int rcode;
     if ((rcode = ensure(ctx, ctx->lti[4], group * n * dd * sizeof(double)))) return rcode;
     if ((rcode = ensure(ctx, ctx->lti[6], group * n * dd * sizeof(double)))) return rcode;
     if ((rcode = ensure(ctx, ctx->lti[7], group * n * d * sizeof(double)))) return rcode;
-    size_t off = 0;
-    const size_t o_aggA = off;  off = rc_align(off + group * nc * nf * sizeof(double));
-    const size_t o_aggB = off;  off = rc_align(off + group * nc * nf * sizeof(double));
-    const size_t o_sagA = off;  off = rc_align(off + group * nc * ns * sizeof(double));
-    const size_t o_sagB = off;  off = rc_align(off + group * nc * ns * sizeof(double));
-    const size_t o_ll = off;    off = rc_align(off + group * nc * sizeof(double));
-    const size_t o_gp = off;    off = rc_align(off + group * nc * nst * sizeof(double));
-    if ((rcode = ensure(ctx, ctx->ws, off))) return rcode;
-    char* base = (char*)ctx->ws.p;
-    double *aggA = (double*)(base + o_aggA), *aggB = (double*)(base + o_aggB);
-    double *sagA = (double*)(base + o_sagA), *sagB = (double*)(base + o_sagB);
+    const GradLtiParts p = grad_lti_lay(c, group, nc, nf, ns, nst);
+    Scratch s;
+    if ((rcode = commit(ctx, ctx->ws, c, &s))) return rcode;
+    double *aggA = s(p.aggA), *aggB = s(p.aggB), *sagA = s(p.sagA), *sagB = s(p.sagB);
     double* Fs = (double*)ctx->lti[4].p;
     for (size_t g0 = 0; g0 < (size_t)B; g0 += group) {
         const int G = (int)((size_t)B - g0 < group ? (size_t)B - g0 : group);
@@ -2732,7 +2702,7 @@ int launch_ll_grad_lti_batch(pgps_ctx* ctx, long N, int d, int B, const double* 
         a.seg_first = 1; a.seg_last = 1; a.implicit_q = 1; a.store_f = 0;
         a.batch = G; a.bs_F = (long)(n * dd); a.bs_agg = (long)(nc * nf); a.bs_model = bs_model;
         a.Rs = tab + 2 * dd + d;                        // R of model b at tab[b * bs_model + 2 dd + d]
-        a.llpart = (double*)(base + o_ll);
+        a.llpart = s(p.ll);
         a.agg1 = aggA;
         if ((rcode = rc::level1(ctx, d, a, 0))) return rcode;
         double* pre = aggA;
@@ -2741,7 +2711,7 @@ int launch_ll_grad_lti_batch(pgps_ctx* ctx, long N, int d, int B, const double* 
         g.N = N; g.d = d; g.Lw = lw; g.nchunk = nchunk;
         g.Pinf = tab + dd; g.H = tab + 2 * dd; g.R = 0.0; g.Fs = Fs; g.ys = ys; g.ts = ts; g.t0 = t0;
         g.fPs = (double*)ctx->lti[6].p; g.fms = (double*)ctx->lti[7].p;
-        g.pre = pre; g.sagg = sagA; g.llpart = a.llpart; g.gpart = (double*)(base + o_gp);
+        g.pre = pre; g.sagg = sagA; g.llpart = a.llpart; g.gpart = s(p.gp);
         g.out = out + g0 * (1 + nst);
         g.batch = G; g.table = tab; g.bs_model = bs_model;
         g.bs_F = (long)(n * dd); g.bs_fm = (long)(n * d); g.bs_pre = (long)(nc * nf); g.bs_sagg = (long)(nc * ns);

@@ -7,7 +7,7 @@ min / median / max over all repeats of all rounds.  Writes profiles/predict_batc
     python tools/predict_batch_bench.py [--baseline-lib PATH] [--rounds 3] [--reps 5] [--out PATH] [--forms]
 
 --forms adds, for the Matern shapes, the batch under pgps_set_batch_form 1 and 2 and under scratch budgets of 8 MiB to
-1 GiB (the numbers behind the automatic form and kBatchScratchDefault, csrc/pgps_internal.h), and for B <= 10 the batched
+1 GiB (the numbers behind the automatic form and kBatchScratchDefault, csrc/pgps_scratch.h), and for B <= 10 the batched
 launches forced (the number behind StateSpaceGP._PREDICT_BATCH_FROM)."""
 import argparse
 import json
