@@ -562,6 +562,36 @@ int pgps_pkfs_seg_dev_f64(pgps_ctx*, long N, int d, const double* P0, const doub
 int pgps_pkfs_seg_dev_f32(pgps_ctx*, long N, int d, const float* P0, const float* Fs, const float* Qs, const float* H,
                           float R, const float* ys, float* fms, float* fPs, float* sms, float* sPs, double* ll);
 
+/* ---- observations with error bars: per-observation noise variances (fused path, fp64, d <= 3) ----------
+ * The model  y_k = H x_k + e_k,  e_k ~ N(0, R + rs[k]):  `rs` (N) are GIVEN variances (the squares of the error bars), R the one
+ * shared, trainable jitter.  Each entry point is its scalar namesake (pgps_gp_dev_f64 with only ll asked for /
+ * pgps_gp_predict_f64 / pgps_gp_ll_grad_adj_dev_f64) with `rs` behind `ys`; out = [ll | Abar | Ubar | Hbar | Rbar] as
+ * pgps_gp_ll_grad_adj_dev_f64 lays it out, Rbar = d ll / d R = sum_k d ll / d (R + rs[k]).  The predict call merges the sorted
+ * ts and tq as pgps_gp_predict_* does (equal times: the shorter array's point first) and carries ys and rs through the merge.
+ * rs[k] is read at observed steps only: where ys[k] is NaN it may hold anything, NaN included.  R >= 0 is accepted; the
+ * requirement is rs[k] finite, rs[k] >= 0 and R + rs[k] > 0 at every observed step.  The host-array forms scan rs once and
+ * return PGPS_E_INVALID where that fails; for the _dev forms (device pointers ts, ys, rs, tq, mean, var, ll / out; asynchronous on
+ * the context's stream) it is a PRECONDITION.  A null pointer (rs included), N < 1, K < 1, lam <= 0, R < 0 or not finite:
+ * PGPS_E_INVALID; d outside 1..3: PGPS_E_UNSUPPORTED_DIM; host forms: a non-finite ll: PGPS_E_NUMERIC.  Three launches per
+ * call whatever N (pgps_set_chunk honoured; pgps_set_one_launch and pgps_set_resident do not apply). */
+int pgps_gp_ll_het_f64(pgps_ctx*, long N, int d, double lam, const double* N1, const double* N2, const double* Pinf,
+                       const double* H, double R, const double* ts, const double* ys, const double* rs, double t0, double* ll);
+int pgps_gp_ll_het_dev_f64(pgps_ctx*, long N, int d, double lam, const double* N1, const double* N2, const double* Pinf,
+                           const double* H, double R, const double* ts, const double* ys, const double* rs, double t0,
+                           double* ll);
+int pgps_gp_predict_het_f64(pgps_ctx*, long N, long K, int d, double lam, const double* N1, const double* N2,
+                            const double* Pinf, const double* H, double R, const double* ts, const double* ys,
+                            const double* rs, double t0, const double* tq, double* mean, double* var, double* ll);
+int pgps_gp_predict_het_dev_f64(pgps_ctx*, long N, long K, int d, double lam, const double* N1, const double* N2,
+                                const double* Pinf, const double* H, double R, const double* ts, const double* ys,
+                                const double* rs, double t0, const double* tq, double* mean, double* var, double* ll);
+int pgps_gp_ll_grad_adj_het_f64(pgps_ctx*, long N, int d, double lam, const double* N1, const double* N2, const double* Pinf,
+                                const double* H, double R, const double* ts, double t0, const double* ys, const double* rs,
+                                double* out /* 1 + d d + 2 d + 1 */);
+int pgps_gp_ll_grad_adj_het_dev_f64(pgps_ctx*, long N, int d, double lam, const double* N1, const double* N2,
+                                    const double* Pinf, const double* H, double R, const double* ts, double t0,
+                                    const double* ys, const double* rs, double* out /* 1 + d d + 2 d + 1 */);
+
 /* ---- sequential mode: pssgp/kalman/sequential.py:11-73 (kf, ks) ------------------------
  * StateSpaceGP(parallel=False).  Host arithmetic on HOST pointers, as in the reference (its
  * sequential mode is the CPU `tf.scan`).  No context needed.  mps / Pps (predicted moments,
@@ -570,6 +600,11 @@ int pgps_seq_kf_f64(long N, int d, const double* P0, const double* Fs, const dou
                     double R, const double* ys, double* fms, double* fPs, double* ll, double* mps, double* Pps);
 int pgps_seq_kf_f32(long N, int d, const float* P0, const float* Fs, const float* Qs, const float* H, float R,
                     const float* ys, float* fms, float* fPs, double* ll, float* mps, float* Pps);
+/* ... with the noise variance of EVERY step, Rs (N), in place of R (read where ys[k] is not NaN only; null: PGPS_E_INVALID) */
+int pgps_seq_kf_het_f64(long N, int d, const double* P0, const double* Fs, const double* Qs, const double* H,
+                        const double* Rs, const double* ys, double* fms, double* fPs, double* ll, double* mps, double* Pps);
+int pgps_seq_kf_het_f32(long N, int d, const float* P0, const float* Fs, const float* Qs, const float* H, const float* Rs,
+                        const float* ys, float* fms, float* fPs, double* ll, float* mps, float* Pps);
 int pgps_seq_ks_f64(long N, int d, const double* Fs, const double* ms, const double* Ps, const double* mps,
                     const double* Pps, double* sms, double* sPs);
 int pgps_seq_ks_f32(long N, int d, const float* Fs, const float* ms, const float* Ps, const float* mps,

@@ -62,6 +62,35 @@ __device__ __forceinline__ void gp_prior(const GpModel<T>& m, T* h, T* P0 /*sym*
 }
 
 // ---------------------------------------------------------------------------------------------
+// per-observation noise variances: a compile-time flavour of the bodies below, HET, off by default --
+// the scalar instantiations are what they were.  With HET a body takes `rs` (N given variances s_k), a lane loads rs[k + 1]
+// next to its prefetch of ts[k + 1], ys[k + 1], and the step's noise variance is R + s_k.  At a missing step the loaded value
+// never reaches the add (it may be NaN).  Instantiated in pgps_het_inst.hip only.
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ T het_noise(T R, T r, T y) {
+    return R + (is_nan(y) ? T(0) : r);
+}
+
+// filter_apply_step (pgps_kernels.hip.h) in its (E, g, L) form with the step's noise variance as an argument
+template <typename T, int D, bool SMOOTH>
+__device__ __forceinline__ void gp_apply_step_r(const ScanArgs<T>& a, long k, long k0, const T* F, const T* Qf, T y, const T* h,
+                                                T R, MeanCov<T, D>& s, LogLik& ll, SmthElem<T, D>& sagg) {
+    constexpr int MAT = D * D, SYM = Dim<D>::SYM;
+    T Q[SYM];
+    sym_from_full<T, D>(Qf, Q);
+    T mp[D], Pp[SYM], FP[MAT];
+    MeanCov<T, D> prev = s;
+    kf_step(s, F, Q, y, h, R, (k == 0) && a.seg_first, ll, mp, Pp, FP);
+    if (SMOOTH && k > k0) {                 // element of step k-1 from this step's predict
+        SmthElem<T, D> e, r;
+        smth_element(prev, mp, Pp, FP, e);
+        smth_combine(sagg, e, r);
+        sagg = r;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // reduce
 // ---------------------------------------------------------------------------------------------
 // LDS of the fused kernels: declared once per kernel and handed to the bodies, so that the one-launch kernel (below), which
@@ -76,8 +105,8 @@ struct GpLds {
     __attribute__((aligned(16))) char stage[kWaves][GF::BYTES + GM::BYTES];
 };
 
-template <typename T, int D>
-__device__ __forceinline__ void gp_reduce_body(const GpArgs<T>& g, T* lds) {
+template <typename T, int D, bool HET = false>
+__device__ __forceinline__ void gp_reduce_body(const GpArgs<T>& g, T* lds, const T* rs = nullptr) {
     constexpr int MAT = D * D, SYM = Dim<D>::SYM;
     using FE = FiltElem<T, D>;
     const ScanArgs<T>& a = g.s;
@@ -91,16 +120,24 @@ __device__ __forceinline__ void gp_reduce_body(const GpArgs<T>& g, T* lds) {
     if (k0 < k1) {
         T tprev = (k0 > 0) ? g.m.ts[k0 - 1] : g.m.t_prev;
         T tn = g.m.ts[k0], yn = a.ys[k0];
+        [[maybe_unused]] T rn = T(0);
+        if constexpr (HET) rn = rs[k0];
         for (long k = k0; k < k1; ++k) {
             const T t = tn, y = yn;
-            if (k + 1 < k1) { tn = g.m.ts[k + 1]; yn = a.ys[k + 1]; }
+            [[maybe_unused]] const T rk = rn;
+            if (k + 1 < k1) {
+                tn = g.m.ts[k + 1]; yn = a.ys[k + 1];
+                if constexpr (HET) rn = rs[k + 1];
+            }
+            T Rk = a.R;
+            if constexpr (HET) Rk = het_noise(a.R, rk, y);
             if (k == 0) {
-                filt_first(agg, P0, y, h, a.R);
+                filt_first(agg, P0, y, h, Rk);
             } else {
                 T F[MAT], Qf[MAT], Q[SYM];
                 lti_step<T, D>(g.m, t - tprev, F, Qf);
                 sym_from_full<T, D>(Qf, Q);
-                filt_extend(agg, F, Q, y, h, a.R);
+                filt_extend(agg, F, Q, y, h, Rk);
             }
             tprev = t;
         }
@@ -120,8 +157,8 @@ __global__ __launch_bounds__(kBlock) void k_gp_reduce(const GpArgs<T> g) {
 // ---------------------------------------------------------------------------------------------
 // apply (+ log-likelihood, + smoothing aggregates when SMOOTH); fms / fPs are written when non-null
 // ---------------------------------------------------------------------------------------------
-template <typename T, int D, bool SMOOTH, bool NT>
-__device__ __forceinline__ void gp_apply_body(const GpArgs<T>& g, GpLds<T, D>& sh) {
+template <typename T, int D, bool SMOOTH, bool NT, bool HET = false>
+__device__ __forceinline__ void gp_apply_body(const GpArgs<T>& g, GpLds<T, D>& sh, const T* rs = nullptr) {
     constexpr int MAT = D * D, SYM = Dim<D>::SYM, NF = Dim<D>::NFILT, G = 4;
     using FE = FiltElem<T, D>;
     using SE = SmthElem<T, D>;
@@ -155,10 +192,12 @@ __device__ __forceinline__ void gp_apply_body(const GpArgs<T>& g, GpLds<T, D>& s
     if (blockIdx.x > 0 && !shortcut) fold_spine_partial<FE>(a.spine, 0, (int)blockIdx.x, left_part);
     ws_load(a.lpre, a.nlanes, gt, lp);
     T tprev = T(0), tn = T(0), yn = T(0);
+    [[maybe_unused]] T rn = T(0);
     if (k0 < k1) {
         tprev = (k0 > 0) ? g.m.ts[k0 - 1] : g.m.t_prev;
         tn = g.m.ts[k0];
         yn = a.ys[k0];
+        if constexpr (HET) rn = rs[k0];
     }
     if (shortcut) {
         s = s_short;
@@ -180,12 +219,17 @@ __device__ __forceinline__ void gp_apply_body(const GpArgs<T>& g, GpLds<T, D>& s
     if (k0 < k1) {
         for (long k = k0; k < k1; ++k) {
             const T t = tn, y = yn;
+            [[maybe_unused]] const T rk = rn;
             if (k + 1 < a.N && (k + 1 < k1 || SMOOTH)) tn = g.m.ts[k + 1];
-            if (k + 1 < k1) yn = a.ys[k + 1];
+            if (k + 1 < k1) {
+                yn = a.ys[k + 1];
+                if constexpr (HET) rn = rs[k + 1];
+            }
             T F[MAT], Qf[MAT];
             lti_step<T, D>(g.m, t - tprev, F, Qf);
             tprev = t;
-            filter_apply_step<T, D, SMOOTH>(a, k, k0, F, Qf, y, h, s, ll, sagg);
+            if constexpr (HET) gp_apply_step_r<T, D, SMOOTH>(a, k, k0, F, Qf, y, h, het_noise(a.R, rk, y), s, ll, sagg);
+            else filter_apply_step<T, D, SMOOTH>(a, k, k0, F, Qf, y, h, s, ll, sagg);
             if (store) {
                 T Pf[MAT];
                 full_from_sym<T, D>(s.P, Pf);

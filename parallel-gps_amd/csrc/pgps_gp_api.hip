@@ -181,11 +181,13 @@ __device__ __forceinline__ long merge_path_block(const T* A, long nA, const T* B
     return lo;
 }
 
-template <typename T>
+// HET (pgps_gp_predict_het_*): a second payload of the training steps, rs -> rs_m, takes the road of ys (NaN at query rows)
+template <typename T, bool HET = false>
 __global__ __launch_bounds__(kBlock) void k_merge_sorted(long N, long K, const T* ts, const T* ys, const T* tq, T* ts_m,
-                                                          T* ys_m, int* qslot) {
+                                                          T* ys_m, int* qslot, const T* rs = nullptr, T* rs_m = nullptr) {
     __shared__ T s_t[kMergeTile];           // A's part of the tile, then B's
     __shared__ T s_y[kMergeTile];           // observations of the training part
+    __shared__ T s_r[HET ? kMergeTile : 1];
     const bool query_first = (N >= K);      // A = the queries when they are the shorter array
     const T* A = query_first ? tq : ts;
     const T* B = query_first ? ts : tq;
@@ -200,6 +202,7 @@ __global__ __launch_bounds__(kBlock) void k_merge_sorted(long N, long K, const T
         s_t[e] = inA ? A[g] : B[g];
         const bool training = (inA != query_first);
         s_y[e] = training ? ys[g] : (T)__builtin_nan("");
+        if constexpr (HET) s_r[e] = training ? rs[g] : (T)__builtin_nan("");
     }
     __syncthreads();
     // this lane's kMergeItems consecutive outputs: cut of its first diagonal inside the tile, then a serial merge
@@ -212,15 +215,18 @@ __global__ __launch_bounds__(kBlock) void k_merge_sorted(long N, long K, const T
     }
     int ia = lo, ib = ld - lo;
     T rt[kMergeItems], ry[kMergeItems];
+    [[maybe_unused]] T rr[kMergeItems];
     int rq[kMergeItems];
 #pragma unroll
     for (int r = 0; r < kMergeItems; ++r) {
         rt[r] = T(0); ry[r] = T(0); rq[r] = -1;
+        if constexpr (HET) rr[r] = T(0);
         if (ld + r < n) {
             const bool takeA = ib >= nb || (ia < na && s_t[ia] <= s_t[na + ib]);
             const int e = takeA ? ia : na + ib;
             rt[r] = s_t[e];
             ry[r] = s_y[e];
+            if constexpr (HET) rr[r] = s_r[e];
             rq[r] = (takeA == query_first) ? (int)(takeA ? a0 + ia : b0 + ib) : -1;
             if (takeA) ++ia; else ++ib;
         }
@@ -231,8 +237,12 @@ __global__ __launch_bounds__(kBlock) void k_merge_sorted(long N, long K, const T
         store_vec<T, kMergeItems>(ts_m + o, rt);
         store_vec<T, kMergeItems>(ys_m + o, ry);
         store_vec<int, kMergeItems>(qslot + o, rq);
+        if constexpr (HET) store_vec<T, kMergeItems>(rs_m + o, rr);
     } else {
-        for (int r = 0; r < kMergeItems && ld + r < n; ++r) { ts_m[o + r] = rt[r]; ys_m[o + r] = ry[r]; qslot[o + r] = rq[r]; }
+        for (int r = 0; r < kMergeItems && ld + r < n; ++r) {
+            ts_m[o + r] = rt[r]; ys_m[o + r] = ry[r]; qslot[o + r] = rq[r];
+            if constexpr (HET) rs_m[o + r] = rr[r];
+        }
     }
 }
 
@@ -247,6 +257,17 @@ int launch_merge(pgps_ctx* ctx, long N, long K, const T* ts, const T* ys, const 
 }
 template int launch_merge<double>(pgps_ctx*, long, long, const double*, const double*, const double*, double*, double*, int*);
 template int launch_merge<float>(pgps_ctx*, long, long, const float*, const float*, const float*, float*, float*, int*);
+
+// the same merge with rs woven next to ys (rs_m 16-byte aligned, as the other outputs are)
+int launch_merge_het(pgps_ctx* ctx, long N, long K, const double* ts, const double* ys, const double* rs, const double* tq,
+                     double* ts_m, double* ys_m, double* rs_m, int* qslot) {
+    RoctxRange range_("merge_sorted");
+    const long M = N + K;
+    const dim3 grid((unsigned)((M + kMergeTile - 1) / kMergeTile)), block(kBlock);
+    k_merge_sorted<double, true><<<grid, block, 0, ctx->stream>>>(N, K, ts, ys, tq, ts_m, ys_m, qslot, rs, rs_m);
+    HIPCHK(ctx, hipGetLastError());
+    return PGPS_OK;
+}
 
 }  // namespace pgps
 

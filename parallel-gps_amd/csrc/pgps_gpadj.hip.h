@@ -73,8 +73,10 @@ __device__ __forceinline__ void adj_step(const GpModel<double>& m, double dt, co
 // ---------------------------------------------------------------------------------------------
 // forward: filter, log-likelihood, kept states, adjoint elements
 // ---------------------------------------------------------------------------------------------
-template <int D>
-__device__ __forceinline__ void gp_gfwd_body(const GpAdjArgs& ga, GpLds<double, D>& sh) {
+// HET (both bodies): per-observation noise variances, R + rs[k] at an observed step (pgps_fused.hip.h het_noise; instantiated
+// in pgps_het_inst.hip).  Rbar is accumulated per step either way: d ll / d R = sum_k d ll / d R_k
+template <int D, bool HET = false>
+__device__ __forceinline__ void gp_gfwd_body(const GpAdjArgs& ga, GpLds<double, D>& sh, const double* rs = nullptr) {
     using T = double;
     constexpr int MAT = D * D, SYM = Dim<D>::SYM, NX = D + SYM;
     using FE = FiltElem<T, D>;
@@ -111,9 +113,15 @@ __device__ __forceinline__ void gp_gfwd_body(const GpAdjArgs& ga, GpLds<double, 
     if (k0 < k1) {
         T tprev = (k0 > 0) ? g.m.ts[k0 - 1] : g.m.t_prev;
         T tn = g.m.ts[k0], yn = a.ys[k0];
+        [[maybe_unused]] T rn = T(0);
+        if constexpr (HET) rn = rs[k0];
         for (long k = k0; k < k1; ++k) {
             const T t = tn, y = yn;
-            if (k + 1 < k1) { tn = g.m.ts[k + 1]; yn = a.ys[k + 1]; }
+            [[maybe_unused]] const T rk = rn;
+            if (k + 1 < k1) {
+                tn = g.m.ts[k + 1]; yn = a.ys[k + 1];
+                if constexpr (HET) rn = rs[k + 1];
+            }
             // the state entering the step: what the reverse pass starts the step from
             {
                 double* x = ga.xs + (long)(k - k0) * NX * a.nlanes + gt;
@@ -123,7 +131,9 @@ __device__ __forceinline__ void gp_gfwd_body(const GpAdjArgs& ga, GpLds<double, 
                 for (int i = 0; i < SYM; ++i) x[(long)(D + i) * a.nlanes] = s.P[i];
             }
             AdjStep<D> st;
-            adj_step<D>(g.m, t - tprev, s, y, h, a.R, st);
+            T Rk = a.R;
+            if constexpr (HET) Rk = het_noise(a.R, rk, y);
+            adj_step<D>(g.m, t - tprev, s, y, h, Rk, st);
             tprev = t;
             if (st.obs) ll.add(st.r, st.S);
             // filtered state of the step
@@ -178,8 +188,8 @@ __global__ __launch_bounds__(kBlock) void k_gp_gfwd(const GpAdjArgs ga) {
 // ---------------------------------------------------------------------------------------------
 // backward: the reverse sweep
 // ---------------------------------------------------------------------------------------------
-template <int D>
-__device__ __forceinline__ void gp_gback_body(const GpAdjArgs& ga, GpLds<double, D>& sh) {
+template <int D, bool HET = false>
+__device__ __forceinline__ void gp_gback_body(const GpAdjArgs& ga, GpLds<double, D>& sh, const double* rs = nullptr) {
     using T = double;
     constexpr int MAT = D * D, SYM = Dim<D>::SYM, NX = D + SYM, NST = gp_adj_nstat<D>();
     using SE = SmthElem<T, D>;
@@ -242,7 +252,9 @@ __device__ __forceinline__ void gp_gback_body(const GpAdjArgs& ga, GpLds<double,
             }
             const T dt = t - tp;
             AdjStep<D> q;
-            adj_step<D>(g.m, dt, s, y, h, a.R, q);
+            T Rk = a.R;
+            if constexpr (HET) Rk = het_noise(a.R, rs[k], y);
+            adj_step<D>(g.m, dt, s, y, h, Rk, q);
             T BK[D], ubar[D], mpbar[D], Ppbar[SYM];
             sym_vec<T, D>(B, q.K, BK);
             T aK = T(0), KBK = T(0);

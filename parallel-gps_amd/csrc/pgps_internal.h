@@ -341,6 +341,18 @@ int launch_gp_multi_grad(pgps_ctx* ctx, GpMultiArgs a, double* out);
 template <typename T>
 int launch_merge(pgps_ctx* ctx, long N, long K, const T* ts, const T* ys, const T* tq, T* ts_m, T* ys_m, int* qslot);
 
+// ... with a second payload, rs -> rs_m (per-observation noise variances, NaN at the query rows)
+int launch_merge_het(pgps_ctx* ctx, long N, long K, const double* ts, const double* ys, const double* rs, const double* tq,
+                     double* ts_m, double* ys_m, double* rs_m, int* qslot);
+
+// per-observation noise variances on the fused path (pgps_het_inst.hip; fp64, d <= 3, three-launch forms): step k is observed
+// with variance g.s.R + rs[k].  launch_gp_het: the log-likelihood (g.qslot null, g.s.ll set) or predict_f over a merged
+// series (g.qslot, g.pmean, g.pvar, g.s.fms, g.s.fPs set); launch_gp_adj_het: out = [ll | Abar | Ubar | Hbar | Rbar] [device]
+template <int D>
+int launch_gp_het(pgps_ctx* ctx, GpArgs<double> g, const double* rs);
+template <int D>
+int launch_gp_adj_het(pgps_ctx* ctx, GpArgs<double> g, const double* rs, double* out);
+
 // log-likelihood + gradient on the fused path (pgps_grad.hip); all array pointers device
 int launch_grad(pgps_ctx* ctx, long N, int d, int np, const double* model, const double* ts, double t0,
                 const double* ys, double* out_dev);

@@ -37,10 +37,10 @@ struct Seq {
     }
 };
 
-// sequential.py:11-47
+// sequential.py:11-47.  Rs (N) non-null: the noise variance of step k is Rs[k] (pgps_seq_kf_het_*), read at observed steps only
 template <typename T>
 int seq_kf(long N, int d, const T* P0, const T* Fs, const T* Qs, const T* H, T R, const T* ys, T* fms, T* fPs,
-           double* ll, T* mps, T* Pps) {
+           double* ll, T* mps, T* Pps, const T* Rs = nullptr) {
     if (N < 1 || d < 1 || !P0 || !Fs || !Qs || !H || !ys || !fms || !fPs) return PGPS_E_INVALID;
     const size_t dd = (size_t)d * d;
     Seq<T> w(d);
@@ -57,7 +57,7 @@ int seq_kf(long N, int d, const T* P0, const T* Fs, const T* Qs, const T* H, T R
         w.predict(F, P.data(), Q, Pp.data());
         const T y = ys[k];
         if (y == y) {
-            T S = R, yp = 0;
+            T S = Rs ? Rs[k] : R, yp = 0;
             for (int i = 0; i < d; ++i) {
                 T acc = 0;
                 for (int j = 0; j < d; ++j) acc += Pp[i * d + j] * H[j];
@@ -377,6 +377,17 @@ extern "C" int pgps_seq_kf_f64(long N, int d, const double* P0, const double* Fs
 extern "C" int pgps_seq_kf_f32(long N, int d, const float* P0, const float* Fs, const float* Qs, const float* H,
                                float R, const float* ys, float* fms, float* fPs, double* ll, float* mps, float* Pps) {
     return seq_kf<float>(N, d, P0, Fs, Qs, H, R, ys, fms, fPs, ll, mps, Pps);
+}
+extern "C" int pgps_seq_kf_het_f64(long N, int d, const double* P0, const double* Fs, const double* Qs, const double* H,
+                                   const double* Rs, const double* ys, double* fms, double* fPs, double* ll, double* mps,
+                                   double* Pps) {
+    if (!Rs) return PGPS_E_INVALID;
+    return seq_kf<double>(N, d, P0, Fs, Qs, H, 0.0, ys, fms, fPs, ll, mps, Pps, Rs);
+}
+extern "C" int pgps_seq_kf_het_f32(long N, int d, const float* P0, const float* Fs, const float* Qs, const float* H,
+                                   const float* Rs, const float* ys, float* fms, float* fPs, double* ll, float* mps, float* Pps) {
+    if (!Rs) return PGPS_E_INVALID;
+    return seq_kf<float>(N, d, P0, Fs, Qs, H, 0.0f, ys, fms, fPs, ll, mps, Pps, Rs);
 }
 extern "C" int pgps_seq_ks_f64(long N, int d, const double* Fs, const double* ms, const double* Ps, const double* mps,
                                const double* Pps, double* sms, double* sPs) {

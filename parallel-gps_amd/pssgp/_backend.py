@@ -155,6 +155,14 @@ def _declare(lib):
         for dev in ("", "_dev"):
             getattr(lib, f"pgps_gp_ll_grad_multi{dev}_f64").argtypes = [P, c_long, c_int, c_int, c_double, P, P, P, P, c_double, P,
                                                                        P, c_double, P]
+    if hasattr(lib, "pgps_gp_ll_het_f64"):              # (absent from libraries built before per-observation variances)
+        for dev in ("", "_dev"):
+            getattr(lib, f"pgps_gp_ll_het{dev}_f64").argtypes = [P, c_long, c_int, c_double, P, P, P, P, c_double, P, P, P,
+                                                                c_double, P]
+            getattr(lib, f"pgps_gp_predict_het{dev}_f64").argtypes = [P, c_long, c_long, c_int, c_double, P, P, P, P, c_double,
+                                                                     P, P, P, c_double, P, P, P, P]
+            getattr(lib, f"pgps_gp_ll_grad_adj_het{dev}_f64").argtypes = [P, c_long, c_int, c_double, P, P, P, P, c_double, P,
+                                                                         c_double, P, P, P]
     return lib
 
 
@@ -793,6 +801,64 @@ def gp_ll_grad_multi(form, Pinf, H, R, ts, Y, t0=0.0, device=0):
     dd = d * d
     st = out[M:]
     return out[:M].copy(), st[:dd].reshape(d, d).copy(), st[dd:dd + d].copy(), st[dd + d:dd + 2 * d].copy(), float(st[dd + 2 * d])
+
+
+def _het_inputs(form, Pinf, H, ts, ys, rs):
+    lam, N1, N2 = form
+    ts_a = _prep(ts, np.float64, (-1,))
+    ys_a = _prep(ys, np.float64, (-1,))
+    rs_a = _prep(rs, np.float64, (-1,))
+    N = ts_a.shape[0]
+    if ys_a.shape[0] != N or rs_a.shape[0] != N:
+        raise ValueError(f"observations has {ys_a.shape[0]} rows, observation variances {rs_a.shape[0]}, the series {N} steps")
+    d = N1.shape[0]
+    model = (c_double(lam), _ptr(_prep(N1, np.float64)), _ptr(_prep(N2, np.float64)), _ptr(_prep(Pinf, np.float64, (d, d))),
+             _ptr(_prep(H, np.float64, (d,))))
+    return ts_a, ys_a, rs_a, d, model
+
+
+def _het_context(device):
+    ctx = get_context(device)
+    if not hasattr(ctx.lib, "pgps_gp_ll_het_f64"):
+        raise RuntimeError("this libpgps has no pgps_gp_*_het_* entry points")
+    return ctx
+
+
+def gp_ll_het(form, Pinf, H, R, ts, ys, rs, t0=0.0, device=0):
+    """Log-likelihood of a series whose observation k has noise variance R + rs[k] (pgps_gp_ll_het_f64): `rs` (N,) given
+    per-observation variances, finite and >= 0 at the observed rows (ignored where ys is NaN), R >= 0 the shared jitter,
+    R + rs[k] > 0.  fp64, d <= 3."""
+    ts_a, ys_a, rs_a, d, model = _het_inputs(form, Pinf, H, ts, ys, rs)
+    ll = c_double(0.0)
+    _het_context(device).call("pgps_gp_ll_het_f64", c_long(ts_a.shape[0]), c_int(d), *model, c_double(float(R)), _ptr(ts_a),
+                              _ptr(ys_a), _ptr(rs_a), c_double(float(t0)), ctypes.cast(ctypes.byref(ll), c_void_p))
+    return ll.value
+
+
+def gp_predict_het(form, Pinf, H, R, ts, ys, rs, tq, t0=0.0, device=0):
+    """predict_f under per-observation noise variances R + rs[k] (pgps_gp_predict_het_f64): the merge of the sorted `ts` (N)
+    and `tq` (K) carries ys and rs, the fused filter + smoother runs over the N + K steps.  Returns (mean (K,), var (K,) of
+    f, ll of the training series)."""
+    ts_a, ys_a, rs_a, d, model = _het_inputs(form, Pinf, H, ts, ys, rs)
+    tq_a = _prep(tq, np.float64, (-1,))
+    N, K = ts_a.shape[0], tq_a.shape[0]
+    mean, var = np.empty(K, np.float64), np.empty(K, np.float64)
+    ll = c_double(0.0)
+    _het_context(device).call("pgps_gp_predict_het_f64", c_long(N), c_long(K), c_int(d), *model, c_double(float(R)), _ptr(ts_a),
+                              _ptr(ys_a), _ptr(rs_a), c_double(float(t0)), _ptr(tq_a), _ptr(mean), _ptr(var),
+                              ctypes.cast(ctypes.byref(ll), c_void_p))
+    return mean, var, ll.value
+
+
+def gp_ll_grad_adj_het(form, Pinf, H, R, ts, ys, rs, t0=0.0, device=0):
+    """Log-likelihood and the model's adjoints under per-observation noise variances R + rs[k]
+    (pgps_gp_ll_grad_adj_het_f64): (ll, Abar (d, d), Ubar (d,), Hbar (d,), Rbar), Rbar = d ll / d R = sum_k d ll / d (R + rs[k]);
+    contracted by contract_grad_stats()."""
+    ts_a, ys_a, rs_a, d, model = _het_inputs(form, Pinf, H, ts, ys, rs)
+    out = np.zeros(1 + d * d + 2 * d + 1, np.float64)
+    _het_context(device).call("pgps_gp_ll_grad_adj_het_f64", c_long(ts_a.shape[0]), c_int(d), *model, c_double(float(R)),
+                              _ptr(ts_a), c_double(float(t0)), _ptr(ys_a), _ptr(rs_a), _ptr(out))
+    return split_grad_stats(out, d)
 
 
 # state dimensions of the general-LTI device path: row-cooperative kernels up to 16 (batched evaluation only there),

@@ -24,10 +24,14 @@ def _declare(lib):
     for suf, real in (("f64", ctypes.c_double), ("f32", ctypes.c_float)):
         getattr(lib, f"pgps_seq_kf_{suf}").argtypes = [L, I, P, P, P, P, real, P, P, P, P, P, P]
         getattr(lib, f"pgps_seq_ks_{suf}").argtypes = [L, I, P, P, P, P, P, P, P]
+        if hasattr(lib, f"pgps_seq_kf_het_{suf}"):
+            getattr(lib, f"pgps_seq_kf_het_{suf}").argtypes = [L, I, P, P, P, P, P, P, P, P, P, P, P]
     lib._pgps_seq_declared = True
 
 
-def kf(lgssm, observations, return_loglikelihood=False, return_predicted=False):
+def kf(lgssm, observations, return_loglikelihood=False, return_predicted=False, observation_variances=None):
+    """observation_variances (N,): the noise variance of EVERY step (pgps_seq_kf_het_*), in place of the model's R -- read
+    where the observation is not NaN only.  None: the model's R at every step."""
     lib = _backend.load_library()
     _declare(lib)
     dtype = _backend._dtype_of(lgssm)
@@ -38,10 +42,19 @@ def kf(lgssm, observations, return_loglikelihood=False, return_predicted=False):
     mps = np.empty((N, d), dtype) if return_predicted else None
     Pps = np.empty((N, d, d), dtype) if return_predicted else None
     ll = ctypes.c_double(0.0)
-    code = getattr(lib, f"pgps_seq_kf_{suf}")(N, d, _ptr(P0), _ptr(Fs), _ptr(Qs), _ptr(H), real(R), _ptr(ys),
-                                              _ptr(fms), _ptr(fPs), ctypes.cast(ctypes.byref(ll), ctypes.c_void_p),
-                                              _ptr(mps), _ptr(Pps))
-    _backend.check(None, code, "pgps_seq_kf")
+    if observation_variances is not None:
+        Rs = _backend._prep(observation_variances, dtype, (-1,))
+        if Rs.shape[0] != N:
+            raise ValueError(f"observation_variances has {Rs.shape[0]} entries, the series {N} steps")
+        code = getattr(lib, f"pgps_seq_kf_het_{suf}")(N, d, _ptr(P0), _ptr(Fs), _ptr(Qs), _ptr(H), _ptr(Rs), _ptr(ys),
+                                                      _ptr(fms), _ptr(fPs), ctypes.cast(ctypes.byref(ll), ctypes.c_void_p),
+                                                      _ptr(mps), _ptr(Pps))
+        _backend.check(None, code, "pgps_seq_kf_het")
+    else:
+        code = getattr(lib, f"pgps_seq_kf_{suf}")(N, d, _ptr(P0), _ptr(Fs), _ptr(Qs), _ptr(H), real(R), _ptr(ys),
+                                                  _ptr(fms), _ptr(fPs), ctypes.cast(ctypes.byref(ll), ctypes.c_void_p),
+                                                  _ptr(mps), _ptr(Pps))
+        _backend.check(None, code, "pgps_seq_kf")
     out = (fms, fPs)
     if return_loglikelihood:
         out += (np.asarray(ll.value, dtype=dtype),)
@@ -66,8 +79,8 @@ def ks(lgssm, ms, Ps, mps, Pps):
     return sms, sPs
 
 
-def kfs(model, observations):
-    fms, fPs, mps, Pps = kf(model, observations, return_predicted=True)
+def kfs(model, observations, observation_variances=None):
+    fms, fPs, mps, Pps = kf(model, observations, return_predicted=True, observation_variances=observation_variances)
     return ks(model, fms, fPs, mps, Pps)
 
 

@@ -88,6 +88,19 @@ def _single_output_only(fn):
     return wrapper
 
 
+def _no_observation_variances(fn):
+    """The evaluations that exist for one shared noise variance only: NotImplementedError when observation_variances is set."""
+    import functools
+
+    @functools.wraps(fn)
+    def wrapper(self, *args, **kwargs):
+        if self._obs_var is not None:
+            raise NotImplementedError(f"{fn.__name__} is not available with observation_variances set (per-observation noise "
+                                      "variances cover maximum_log_likelihood_objective, predict_f and log_likelihood_and_grad)")
+        return fn(self, *args, **kwargs)
+    return wrapper
+
+
 def _multi_output(route):
     """A model with num_latent_gps > 1 answers this evaluation with its method `route`; a single-output model runs the decorated
     function exactly as before."""
@@ -137,10 +150,25 @@ class StateSpaceGP:
     cheaper than the loop): ONE filter pass and ONE reverse pass on column tiles give the columns' log-likelihoods and the
     adjoints of their sum (_backend.gp_ll_grad_multi -- the reverse sweep's matrices do not depend on y either); method
     "dual" / "differences" and everything off the device route loop;
-    predict_f_samples, predict_f_batch, log_likelihood_batch and log_likelihood_and_grad_batch are single-output."""
+    predict_f_samples, predict_f_batch, log_likelihood_batch and log_likelihood_and_grad_batch are single-output.
 
-    def __init__(self, data, kernel, noise_variance=1.0, parallel=False, max_parallel=10000):
+    observation_variances (N,) or (N, 1), float64: data with error bars, y_k = f(t_k) + e_k, e_k ~ N(0, noise_variance + s_k) --
+    s_k given (finite and >= 0 wherever y is observed; ignored, NaN allowed, at the NaN rows of y), noise_variance the one
+    trainable jitter.  None (the default, and None assigned later) is the model with one shared noise variance, exactly.
+    With variances set, maximum_log_likelihood_objective and predict_f work for every kernel and both modes, and
+    log_likelihood_and_grad (method None / "adjoint") for a single Matern kernel on the device route; two routes, and nothing
+    falls from the first to the second on a failure (a PgpsError propagates):
+      device route   parallel=True, a single Matern-1/2, -3/2 or -5/2 kernel, float64, sorted training (and query) times: the
+                     per-observation flavour of the fused kernels on host arrays (_backend.gp_ll_het / gp_predict_het /
+                     gp_ll_grad_adj_het; never the resident series, which holds no s);
+      host twin      everything else: the sequential filter + smoother with a per-step variance (sequential.kf / kfs with
+                     observation_variances), correct for any kernel.
+    predict_f(full_cov=True), predict_f_samples, predict_f_batch, log_likelihood_batch, log_likelihood_and_grad_batch, gradient
+    methods "dual" / "differences", gradients of other kernels and Y with more than one column raise NotImplementedError."""
+
+    def __init__(self, data, kernel, noise_variance=1.0, parallel=False, max_parallel=10000, observation_variances=None):
         self.noise_variance = float(noise_variance)
+        self._obs_var = None
         dtype = config.default_float()
         ts, ys = data
         ts = np.asarray(ts, dtype=dtype)
@@ -162,6 +190,31 @@ class StateSpaceGP:
         else:
             self._kf = lambda ssm, y: pkf(ssm, y, return_loglikelihood=True, max_parallel=ts.shape[0])
             self._kfs = lambda ssm, y: pkfs(ssm, y, max_parallel=max_parallel)
+        self.observation_variances = observation_variances
+
+    @property
+    def observation_variances(self):
+        """The given per-observation noise variances s (N,), or None (class docstring)."""
+        return self._obs_var
+
+    @observation_variances.setter
+    def observation_variances(self, value):
+        self._obs_var = None if value is None else self._checked_obs_var(value, self._data[1])
+
+    def _checked_obs_var(self, value, ys):
+        if self.num_latent_gps > 1:
+            raise NotImplementedError("observation_variances covers single-output models; this one has "
+                                      f"{self.num_latent_gps} output columns")
+        s = np.array(value, dtype=np.float64)
+        if s.ndim == 2 and s.shape[1] == 1:
+            s = s[:, 0]
+        n = ys.shape[0]
+        if s.ndim != 1 or s.shape[0] != n:
+            raise ValueError(f"observation_variances must have shape ({n},) or ({n}, 1) like the data, got {np.shape(value)}")
+        seen = s[~np.isnan(ys[:, 0])]
+        if not (np.all(np.isfinite(seen)) and np.all(seen >= 0.0)):
+            raise ValueError("observation_variances must be finite and >= 0 wherever y is observed")
+        return np.ascontiguousarray(s)
 
     @property
     def data(self):
@@ -182,6 +235,8 @@ class StateSpaceGP:
         if ys.ndim != 2 or ys.shape[1] != self.num_latent_gps:
             raise ValueError(f"the model has {self.num_latent_gps} output column(s) (fixed at construction), the new "
                              f"observations have shape {ys.shape}")
+        if self._obs_var is not None:
+            self._checked_obs_var(self._obs_var, ys)        # (length and values against the NEW data)
         self._data = ts, ys
         self._columns = None
         self.invalidate_device_series()
@@ -541,6 +596,10 @@ class StateSpaceGP:
         merge train and query times, mark queries as missing, smooth, keep the query rows,
         project through H.  full_cov=True: the mean (K, 1) and the joint posterior covariance (1, K, K) of f(Xnew)
         (GPflow's [num_latent, K, K]; _predict_f_full_cov) -- the law of predict_f_samples' draws."""
+        if self._obs_var is not None:
+            if full_cov:
+                raise NotImplementedError("predict_f(full_cov=True) is not available with observation_variances set")
+            return self._het_predict_f(Xnew)
         if full_cov:
             return self._predict_f_full_cov(Xnew)
         ts, ys = self.data
@@ -604,6 +663,87 @@ class StateSpaceGP:
         var = np.einsum("ai,nij,aj->na", H, sP, H)
         return mean, var
 
+    # -- per-observation noise variances (class docstring) --------------------------------------------
+    def _het_device_route(self, tq=None):
+        """The fused model (sde-like, form) when the per-observation device route applies, else None: the host twin's."""
+        ts, ys = self.data
+        if not self.parallel or ys.dtype != np.float64 or ts.shape[0] < 1:
+            return None
+        fused = self._matern_forms()
+        if fused is None or not np.all(np.diff(ts.reshape(-1)) >= 0):
+            return None
+        if tq is not None and (tq.size < 1 or tq.dtype != np.float64 or not np.all(np.diff(tq) >= 0)):
+            return None
+        return fused
+
+    def _het_step_variances(self, dtype):
+        """R_k = noise_variance + s_k of every step (the host twin's per-step argument; NaN wherever s is)."""
+        return (np.float64(self.noise_variance) + self._obs_var).astype(dtype)
+
+    def _het_objective(self):
+        ts, Y = self.data
+        fused = self._het_device_route()
+        if fused is not None:
+            from . import _backend
+            sde, form = fused
+            return np.float64(_backend.gp_ll_het(form, sde.P0, sde.H, self.noise_variance, ts.reshape(-1), Y.reshape(-1),
+                                                 self._obs_var))
+        ssm = self._make_model(ts)
+        return kf(ssm, Y, return_loglikelihood=True, observation_variances=self._het_step_variances(Y.dtype))[2]
+
+    def _het_predict_f(self, Xnew):
+        ts, ys = self.data
+        dtype = config.default_float()
+        tq = np.asarray(Xnew, dtype=dtype).reshape(-1)
+        squeezed_ts = ts.reshape(-1)
+        fused = self._het_device_route(tq)
+        if fused is not None:
+            from . import _backend
+            sde, form = fused
+            mean, var, _ = _backend.gp_predict_het(form, sde.P0, sde.H, self.noise_variance, squeezed_ts, ys.reshape(-1),
+                                                   self._obs_var, tq)
+            return mean[:, None], var[:, None]
+        nan_ys = np.full((tq.shape[0], 1), np.nan, dtype=ys.dtype)
+        all_ts, all_ys, all_Rs, all_flags = _merge_sorted(
+            squeezed_ts, tq, (ys, nan_ys), (self._het_step_variances(ys.dtype), np.full(tq.shape, np.nan, dtype=ys.dtype)),
+            (np.zeros(squeezed_ts.shape, dtype=bool), np.ones(tq.shape, dtype=bool)))
+        ssm = self._make_model(all_ts[:, None])
+        sms, sPs = kfs(ssm, all_ys, observation_variances=all_Rs)
+        H = np.asarray(ssm.H)
+        sm, sP = sms[all_flags], sPs[all_flags]
+        return sm @ H.T, np.einsum("ai,nij,aj->na", H, sP, H)
+
+    def _het_ll_and_grad(self, wrt=None, method=None):
+        """log_likelihood_and_grad with observation_variances set: the adjoint pass of the per-observation flavour
+        (_backend.gp_ll_grad_adj_het), contracted as _fused_adjoint_ll_and_grad contracts it -- d ll / d l = -<Abar, F> / l,
+        d ll / d s2 = Ubar^T Pinf H^T / s2, d ll / d noise_variance = Rbar = sum_k d ll / d R_k.  Device route and method None /
+        "adjoint" only; nothing falls back to differences."""
+        if method not in (None, "adjoint"):
+            raise NotImplementedError(f"method = {method!r} is not available with observation_variances set (None or 'adjoint')")
+        fused = self._het_device_route()
+        if fused is None:
+            raise NotImplementedError("gradients with observation_variances set need parallel=True, a single Matern-1/2, -3/2 or "
+                                      "-5/2 kernel, float64 data and sorted times")
+        from . import _backend
+        sde, form = fused
+        ts, Y = self.data
+        lam, N1, _ = form
+        d = N1.shape[0]
+        P0 = np.asarray(sde.P0, np.float64)
+        H = np.asarray(sde.H, np.float64).reshape(-1)
+        ll, Abar, Ubar, _, Rbar = _backend.gp_ll_grad_adj_het(form, P0, H, self.noise_variance, ts.reshape(-1), Y.reshape(-1),
+                                                              self._obs_var)
+        F = np.asarray(N1, np.float64) - float(lam) * np.eye(d)          # F = N1 - lam I
+        k = self.kernel
+        by_name = {"variance": float(Ubar @ (P0 @ H)) / float(k.variance),
+                   "lengthscales": -float(np.sum(Abar * F)) / float(k.lengthscales)}
+        g = np.array([by_name[a] for _, a in leaf_parameters(k)] + [float(Rbar)])
+        if wrt is not None:
+            keep = np.zeros(len(g), bool)
+            keep[[int(i) for i in wrt]] = True
+            g = np.where(keep, g, 0.0)
+        return config.default_float()(ll), g
+
     def _predict_f_full_cov(self, Xnew):
         """predict_f(Xnew, full_cov=True): mean (K, 1) and covariance (1, K, K), symmetric bit for bit, its diagonal the
         variances.  Cov(x_i, x_j | ys) = E_i .. E_{j-1} sP_j between query rows i < j of the merged series (E the smoother
@@ -643,6 +783,7 @@ class StateSpaceGP:
 
     @_single_output_only
     @_public_evaluation
+    @_no_observation_variances
     def predict_f_samples(self, Xnew, num_samples=None, full_cov=True, full_output_cov=False, seed=None):
         """Joint posterior draws of f at `Xnew` (GPflow's predict_f_samples): (S, K, 1), or (K, 1) when num_samples is
         None.  parallel=True: merge, discretisation, filter and a backward-sampling scan on the device for any kernel
@@ -688,6 +829,8 @@ class StateSpaceGP:
     @_multi_output("_multi_objective")
     @_public_evaluation
     def maximum_log_likelihood_objective(self):
+        if self._obs_var is not None:
+            return self._het_objective()
         ts, Y = self.data
         fused, lti = self._device_forms()
         if fused is not None:
@@ -1024,6 +1167,8 @@ class StateSpaceGP:
             raise NotImplementedError("gradients run on the parallel (HIP) path: construct with parallel=True")
         if method not in (None, "adjoint", "dual", "differences"):
             raise ValueError(f"method = {method!r}: None (automatic), 'adjoint', 'dual' or 'differences'")
+        if self._obs_var is not None:
+            return self._het_ll_and_grad(wrt, method)
         from . import _backend
         ts, Y = self.data
         fused, lti = self._device_forms()
@@ -1196,6 +1341,7 @@ class StateSpaceGP:
 
     @_single_output_only
     @_public_evaluation
+    @_no_observation_variances
     def log_likelihood_batch(self, thetas):
         """Marginal log-likelihoods at B hyper-parameter settings in one call: `thetas` is (B, P) in the
         order of `trainable_parameters()`.  The B filters share the series and run side by side on
@@ -1265,6 +1411,7 @@ class StateSpaceGP:
 
     @_single_output_only
     @_public_evaluation
+    @_no_observation_variances
     def predict_f_batch(self, Xnew, thetas, return_log_likelihood=False, reduce=None, weights=None):
         """predict_f at B hyper-parameter settings over the same series and query grid: `thetas` is (B, P) in the order of
         `trainable_parameters()`.  Returns means (B, K, 1) and variances (B, K, 1) -- row b what predict_f(Xnew) returns
@@ -1524,6 +1671,7 @@ class StateSpaceGP:
 
     @_single_output_only
     @_public_evaluation
+    @_no_observation_variances
     def log_likelihood_and_grad_batch(self, thetas, wrt=None):
         """(lls (B,), grads (B, P)): the marginal log-likelihood and its exact gradient at B hyper-parameter settings,
         `thetas` (B, P) in the order of `trainable_parameters()`; row b is what log_likelihood_and_grad() returns with row b
