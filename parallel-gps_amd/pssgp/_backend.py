@@ -487,6 +487,21 @@ def _prep(a, dtype, shape=None):
     return a
 
 
+def _fused_model(form, Pinf, H):
+    """(d, the ctypes arguments (lam, N1, N2, Pinf, H)) of the fused model, as every pgps_gp_* entry point takes them."""
+    lam, N1, N2 = form
+    d = N1.shape[0]
+    return d, (c_double(lam), _ptr(_prep(N1, np.float64)), _ptr(_prep(N2, np.float64)), _ptr(_prep(Pinf, np.float64, (d, d))),
+               _ptr(_prep(H, np.float64, (d,))))
+
+
+def _require(ctx, symbol, family):
+    """`ctx`, for a call of an entry-point family that older builds of the library lack."""
+    if not hasattr(ctx.lib, symbol):
+        raise RuntimeError(f"this libpgps has no {family} entry points")
+    return ctx
+
+
 def discretise(F, Pinf, ts, t0=0.0, device=0):
     """Fs, Qs = expm(dt F), Pinf - Fs Pinf Fs^T on the GPU (host arrays in and out)."""
     dtype = np.asarray(ts).dtype if np.asarray(ts).dtype in (np.float32, np.float64) else np.float64
@@ -693,7 +708,6 @@ def gp(form, Pinf, H, R, ts, ys, t0=0.0, want_filtered=False, want_smoothed=Fals
     """Fused filter (+ smoother) + log-likelihood straight from times and observations.
 
     Returns a dict with "ll" and, on request, "fms", "fPs", "sms", "sPs" (host numpy arrays)."""
-    lam, N1, N2 = form
     ts_a = np.asarray(ts)
     dtype = ts_a.dtype if ts_a.dtype in (np.float32, np.float64) else np.dtype(np.float64)
     suf, _ = _suffix(dtype)
@@ -702,9 +716,7 @@ def gp(form, Pinf, H, R, ts, ys, t0=0.0, want_filtered=False, want_smoothed=Fals
     N = ts_a.shape[0]
     if ys_a.shape[0] != N:
         raise ValueError(f"observations has {ys_a.shape[0]} rows, the series {N} steps")
-    d = N1.shape[0]
-    Pinf = _prep(Pinf, np.float64, (d, d))
-    H = _prep(H, np.float64, (d,))
+    d, model = _fused_model(form, Pinf, H)
     want_filtered = want_filtered or want_smoothed
     out = {}
     fms = np.empty((N, d), dtype) if want_filtered else None
@@ -712,8 +724,7 @@ def gp(form, Pinf, H, R, ts, ys, t0=0.0, want_filtered=False, want_smoothed=Fals
     sms = np.empty((N, d), dtype) if want_smoothed else None
     sPs = np.empty((N, d, d), dtype) if want_smoothed else None
     ll = c_double(0.0)
-    get_context(device).call(f"pgps_gp_{suf}", c_long(N), c_int(d), c_double(lam), _ptr(_prep(N1, np.float64)),
-                             _ptr(_prep(N2, np.float64)), _ptr(Pinf), _ptr(H), c_double(float(R)), _ptr(ts_a),
+    get_context(device).call(f"pgps_gp_{suf}", c_long(N), c_int(d), *model, c_double(float(R)), _ptr(ts_a),
                              c_double(float(t0)), _ptr(ys_a), _ptr(fms), _ptr(fPs), _ptr(sms), _ptr(sPs),
                              ctypes.cast(ctypes.byref(ll), c_void_p))
     out["ll"] = np.asarray(ll.value, dtype=dtype)
@@ -728,7 +739,6 @@ def gp_predict(form, Pinf, H, R, ts, ys, tq, t0=0.0, device=0):
     """predict_f on the device (pgps_gp_predict_*): merge of the sorted `ts` (N) and `tq` (K), fused
     filter + smoother over the N + K steps, posterior mean / variance of f = H x at the K query
     times.  Returns (mean (K,), var (K,), ll of the training series)."""
-    lam, N1, N2 = form
     ts_a = np.asarray(ts)
     dtype = ts_a.dtype if ts_a.dtype in (np.float32, np.float64) else np.dtype(np.float64)
     suf, _ = _suffix(dtype)
@@ -738,27 +748,21 @@ def gp_predict(form, Pinf, H, R, ts, ys, tq, t0=0.0, device=0):
     N, K = ts_a.shape[0], tq_a.shape[0]
     if ys_a.shape[0] != N:
         raise ValueError(f"observations has {ys_a.shape[0]} rows, the series {N} steps")
-    d = N1.shape[0]
+    d, model = _fused_model(form, Pinf, H)
     mean, var = np.empty(K, dtype), np.empty(K, dtype)
     ll = c_double(0.0)
-    get_context(device).call(f"pgps_gp_predict_{suf}", c_long(N), c_long(K), c_int(d), c_double(lam),
-                             _ptr(_prep(N1, np.float64)), _ptr(_prep(N2, np.float64)), _ptr(_prep(Pinf, np.float64, (d, d))),
-                             _ptr(_prep(H, np.float64, (d,))), c_double(float(R)), _ptr(ts_a), _ptr(ys_a),
-                             c_double(float(t0)), _ptr(tq_a), _ptr(mean), _ptr(var),
+    get_context(device).call(f"pgps_gp_predict_{suf}", c_long(N), c_long(K), c_int(d), *model, c_double(float(R)), _ptr(ts_a),
+                             _ptr(ys_a), c_double(float(t0)), _ptr(tq_a), _ptr(mean), _ptr(var),
                              ctypes.cast(ctypes.byref(ll), c_void_p))
     return mean, var, ll.value
 
 
 def _multi_inputs(form, Pinf, H, ts, Y):
-    lam, N1, N2 = form
     ts_a = _prep(ts, np.float64, (-1,))
     Y_a = np.ascontiguousarray(Y, dtype=np.float64)
     if Y_a.ndim != 2 or Y_a.shape[0] != ts_a.shape[0]:
         raise ValueError(f"observations must be (N, M) with N = {ts_a.shape[0]} rows, got shape {Y_a.shape}")
-    d = N1.shape[0]
-    model = (c_double(lam), _ptr(_prep(N1, np.float64)), _ptr(_prep(N2, np.float64)), _ptr(_prep(Pinf, np.float64, (d, d))),
-             _ptr(_prep(H, np.float64, (d,))))
-    return ts_a, Y_a, d, model
+    return (ts_a, Y_a) + _fused_model(form, Pinf, H)
 
 
 def gp_ll_multi(form, Pinf, H, R, ts, Y, t0=0.0, device=0):
@@ -792,9 +796,7 @@ def gp_ll_grad_multi(form, Pinf, H, R, ts, Y, t0=0.0, device=0):
     statistics of sum_j ll[j], contracted by contract_grad_stats().  Rows of Y as gp_ll_multi takes them."""
     ts_a, Y_a, d, model = _multi_inputs(form, Pinf, H, ts, Y)
     N, M = Y_a.shape
-    ctx = get_context(device)
-    if not hasattr(ctx.lib, "pgps_gp_ll_grad_multi_f64"):
-        raise RuntimeError("this libpgps has no pgps_gp_ll_grad_multi_* entry points")
+    ctx = _require(get_context(device), "pgps_gp_ll_grad_multi_f64", "pgps_gp_ll_grad_multi_*")
     out = np.zeros(M + d * d + 2 * d + 1, np.float64)
     ctx.call("pgps_gp_ll_grad_multi_f64", c_long(N), c_int(M), c_int(d), *model, c_double(float(R)), _ptr(ts_a), _ptr(Y_a),
              c_double(float(t0)), _ptr(out))
@@ -804,24 +806,17 @@ def gp_ll_grad_multi(form, Pinf, H, R, ts, Y, t0=0.0, device=0):
 
 
 def _het_inputs(form, Pinf, H, ts, ys, rs):
-    lam, N1, N2 = form
     ts_a = _prep(ts, np.float64, (-1,))
     ys_a = _prep(ys, np.float64, (-1,))
     rs_a = _prep(rs, np.float64, (-1,))
     N = ts_a.shape[0]
     if ys_a.shape[0] != N or rs_a.shape[0] != N:
         raise ValueError(f"observations has {ys_a.shape[0]} rows, observation variances {rs_a.shape[0]}, the series {N} steps")
-    d = N1.shape[0]
-    model = (c_double(lam), _ptr(_prep(N1, np.float64)), _ptr(_prep(N2, np.float64)), _ptr(_prep(Pinf, np.float64, (d, d))),
-             _ptr(_prep(H, np.float64, (d,))))
-    return ts_a, ys_a, rs_a, d, model
+    return (ts_a, ys_a, rs_a) + _fused_model(form, Pinf, H)
 
 
 def _het_context(device):
-    ctx = get_context(device)
-    if not hasattr(ctx.lib, "pgps_gp_ll_het_f64"):
-        raise RuntimeError("this libpgps has no pgps_gp_*_het_* entry points")
-    return ctx
+    return _require(get_context(device), "pgps_gp_ll_het_f64", "pgps_gp_*_het_*")
 
 
 def gp_ll_het(form, Pinf, H, R, ts, ys, rs, t0=0.0, device=0):
@@ -916,9 +911,7 @@ def lti_ll_grad(F, Pinf, H, R, ts, ys, t0=0.0, device=0):
     ys_a = _prep(ys, np.float64, (-1,))
     if ys_a.shape[0] != ts_a.shape[0]:
         raise ValueError(f"observations has {ys_a.shape[0]} rows, the series {ts_a.shape[0]} steps")
-    ctx = get_context(device)
-    if not hasattr(ctx.lib, "pgps_lti_ll_grad_f64"):
-        raise RuntimeError("this libpgps has no pgps_lti_ll_grad_* entry points")
+    ctx = _require(get_context(device), "pgps_lti_ll_grad_f64", "pgps_lti_ll_grad_*")
     out = np.zeros(2 + d * d + 2 * d, np.float64)
     ctx.call("pgps_lti_ll_grad_f64", c_long(ts_a.shape[0]), c_int(d), _ptr(F), _ptr(Pinf), _ptr(H), c_double(float(R)),
              _ptr(ts_a), _ptr(ys_a), c_double(float(t0)), _ptr(out))
@@ -1095,9 +1088,7 @@ class Series:
         ys_a = _prep(ys, np.float64, (-1,))
         if ys_a.shape[0] != ts_a.shape[0]:
             raise ValueError(f"observations has {ys_a.shape[0]} rows, the series {ts_a.shape[0]} steps")
-        lib = self.ctx.lib
-        if not hasattr(lib, "pgps_series_create_f64"):
-            raise RuntimeError("this libpgps has no pgps_series_* entry points")
+        lib = _require(self.ctx, "pgps_series_create_f64", "pgps_series_*").lib
         P = c_void_p
         lib.pgps_series_create_f64.argtypes = [P, c_long, P, P, c_double, ctypes.POINTER(P)]
         lib.pgps_series_set_queries_f64.argtypes = [P, c_long, P]
@@ -1393,9 +1384,7 @@ def gp_ll_grad_adj_batch(models, ts, ys, t0=0.0, device=0):
     if ys_a.shape[0] != ts_a.shape[0]:
         raise ValueError(f"observations has {ys_a.shape[0]} rows, the series {ts_a.shape[0]} steps")
     packed, d = _gp_rows(models)
-    ctx = get_context(device)
-    if not hasattr(ctx.lib, "pgps_gp_ll_grad_adj_batch_f64"):
-        raise RuntimeError("this libpgps has no pgps_gp_ll_grad_adj_batch_* entry points")
+    ctx = _require(get_context(device), "pgps_gp_ll_grad_adj_batch_f64", "pgps_gp_ll_grad_adj_batch_*")
     out = np.empty((packed.shape[0], 2 + d * d + 2 * d), np.float64)
     ctx.call("pgps_gp_ll_grad_adj_batch_f64", c_int(packed.shape[0]), c_long(ts_a.shape[0]), c_int(d), _ptr(packed), _ptr(ts_a),
              c_double(float(t0)), _ptr(ys_a), _ptr(out))
@@ -1421,9 +1410,7 @@ def lti_ll_grad_batch(models, ts, ys, t0=0.0, device=0):
     ys_a = _prep(ys, np.float64, (-1,))
     if ys_a.shape[0] != ts_a.shape[0]:
         raise ValueError(f"observations has {ys_a.shape[0]} rows, the series {ts_a.shape[0]} steps")
-    ctx = get_context(device)
-    if not hasattr(ctx.lib, "pgps_lti_ll_grad_batch_f64"):
-        raise RuntimeError("this libpgps has no pgps_lti_ll_grad_batch_* entry points")
+    ctx = _require(get_context(device), "pgps_lti_ll_grad_batch_f64", "pgps_lti_ll_grad_batch_*")
     out = np.empty((table.shape[0], 2 + d * d + 2 * d), np.float64)
     ctx.call("pgps_lti_ll_grad_batch_f64", c_int(table.shape[0]), c_long(ts_a.shape[0]), c_int(d), _ptr(table), _ptr(ts_a),
              _ptr(ys_a), c_double(float(t0)), _ptr(out))

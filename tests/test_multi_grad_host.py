@@ -109,3 +109,29 @@ def test_automatic_route_bounds():
         assert not pays[name](4096, 2) and pays[name](4096, 3) and pays[name](300, 5)
         assert pays[name](65536, 16) and not pays[name](65537, 16) and not pays[name](2 ** 20, 64)
     assert pays["Matern52"](4096, 2) and pays["Matern52"](131072, 16) and not pays["Matern52"](131073, 16)
+
+
+def test_refusals_and_what_they_count():
+    """The batched evaluations and the draws are single-output and take one shared noise variance.  A multi-output model is
+    refused BEFORE the evaluation is counted (_n_eval decides when the series becomes resident); a single-output model with
+    observation_variances is refused after it.  No library needed."""
+    from pssgp.kernels import Matern32
+    from pssgp.model import StateSpaceGP
+    t, tq, thetas = np.linspace(0.1, 1.0, 8), np.linspace(0.2, 0.9, 3)[:, None], np.array([[1.0, 1.0, 0.1]])
+    calls = {"predict_f_samples": lambda m: m.predict_f_samples(tq, num_samples=2, seed=1),
+             "log_likelihood_batch": lambda m: m.log_likelihood_batch(thetas),
+             "predict_f_batch": lambda m: m.predict_f_batch(tq, thetas),
+             "log_likelihood_and_grad_batch": lambda m: m.log_likelihood_and_grad_batch(thetas)}
+    multi = StateSpaceGP((t, np.zeros((8, 3))), Matern32(1.0, 1.0), 0.1, parallel=True)
+    het = StateSpaceGP((t, np.zeros(8)), Matern32(1.0, 1.0), 0.1, parallel=True, observation_variances=np.full(8, 0.2))
+    for name, call in calls.items():
+        with pytest.raises(NotImplementedError) as e:
+            call(multi)
+        assert str(e.value) == f"{name} covers single-output models; this one has 3 output columns"
+        assert getattr(multi, "_n_eval", 0) == 0
+        before = getattr(het, "_n_eval", 0)
+        with pytest.raises(NotImplementedError) as e:
+            call(het)
+        assert str(e.value) == (f"{name} is not available with observation_variances set (per-observation noise variances cover "
+                                "maximum_log_likelihood_objective, predict_f and log_likelihood_and_grad)")
+        assert het._n_eval == before + 1
