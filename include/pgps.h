@@ -592,6 +592,29 @@ int pgps_gp_ll_grad_adj_het_dev_f64(pgps_ctx*, long N, int d, double lam, const 
                                     const double* Pinf, const double* H, double R, const double* ts, double t0,
                                     const double* ys, const double* rs, double* out /* 1 + d d + 2 d + 1 */);
 
+/* ---- predictive checks of a fitted model against its own data (fused path, fp64, d <= 3) --------------
+ * Two laws of every y_k, from ONE filter and ONE smoother pass over the N training steps (no merge, no query rows):
+ *   osa_mean, osa_var   y_k given the observations BEFORE it: N(H m_k^-, H P_k^- H^T + R), the pair the Kalman pass hands to its
+ *                       log-likelihood accumulator (the first-step rule included); their log densities sum to the log-likelihood;
+ *   loo_mean, loo_var   y_k given ALL OTHER observations (leave-one-out): with (m, v) the smoothed mean and variance of
+ *                       f_k = H x_k,  N((m R - y_k v) / (R - v), R^2 / (R - v)).
+ * Both variances include R.  Where ys[k] is NaN the laws are those of an observation there (leave-one-out: nothing is left
+ * out, N(m, v + R)) and the step adds nothing to either sum.  Each of the four arrays (N doubles) may be NULL: that store is
+ * skipped.  sums[2] = {log-likelihood, sum over the observed steps of log N(y_k | loo_mean, loo_var)} is always written; the
+ * workgroups' partials are added in index order, so equal calls give equal bits, with or without the arrays.  Log densities
+ * per step are not stored: they follow from (y, mean, var).  Arguments as pgps_gp_ll_het_f64 takes them, without rs.
+ * The _dev form takes device pointers (ts, ys, the arrays, sums) and is asynchronous on the context's stream; the host form
+ * copies back only the arrays asked for (none: two doubles).  A null ts / ys / sums, N < 1, lam <= 0, R <= 0 or not finite
+ * (leaving out a noise-free observation is undefined): PGPS_E_INVALID; d outside 1..3: PGPS_E_UNSUPPORTED_DIM; host form: a
+ * non-finite sum: PGPS_E_NUMERIC.  Four launches per call whatever N (pgps_set_chunk honoured; pgps_set_one_launch and
+ * pgps_set_resident do not apply). */
+int pgps_gp_loo_f64(pgps_ctx*, long N, int d, double lam, const double* N1, const double* N2, const double* Pinf,
+                    const double* H, double R, const double* ts, const double* ys, double t0, double* osa_mean, double* osa_var,
+                    double* loo_mean, double* loo_var, double* sums /* 2 */);
+int pgps_gp_loo_dev_f64(pgps_ctx*, long N, int d, double lam, const double* N1, const double* N2, const double* Pinf,
+                        const double* H, double R, const double* ts, const double* ys, double t0, double* osa_mean,
+                        double* osa_var, double* loo_mean, double* loo_var, double* sums /* 2 */);
+
 /* ---- sequential mode: pssgp/kalman/sequential.py:11-73 (kf, ks) ------------------------
  * StateSpaceGP(parallel=False).  Host arithmetic on HOST pointers, as in the reference (its
  * sequential mode is the CPU `tf.scan`).  No context needed.  mps / Pps (predicted moments,

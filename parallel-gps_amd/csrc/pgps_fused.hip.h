@@ -91,6 +91,65 @@ __device__ __forceinline__ void gp_apply_step_r(const ScanArgs<T>& a, long k, lo
 }
 
 // ---------------------------------------------------------------------------------------------
+// predictive checks of a fitted model against its own data: two compile-time flavours, off by default --
+// the other instantiations are what they were.  OSA (gp_apply_body): the Kalman pass stores the one-step-ahead law of y_k,
+// (mu_k, S_k) = (H m_k^-, H P_k^- H^T + R), the pair it hands to the log-likelihood accumulator, at EVERY step (observed or
+// not).  LOO (gp_smooth_body): the smoother projects at every step, reads y_k and removes the factor N(y_k | f_k, R) from the
+// smoothed law of f_k = H x_k (Rasmussen & Williams eq. 5.10-5.12 in cavity form), stores the leave-one-out law of y_k and
+// accumulates its log density; one partial per workgroup (lpd_part), summed afterwards in a fixed order.  Any of the four
+// arrays of GpLooOut (pgps_internal.h) may be null: that store is skipped.  Instantiated in pgps_loo_inst.hip only.
+// ---------------------------------------------------------------------------------------------
+// gp_apply_step_r that also hands out (mu, S) of the step: kf_step's own expressions on the predicted moments it returns
+template <typename T, int D, bool SMOOTH>
+__device__ __forceinline__ void gp_apply_step_osa(const ScanArgs<T>& a, long k, long k0, const T* F, const T* Qf, T y, const T* h,
+                                                  MeanCov<T, D>& s, LogLik& ll, SmthElem<T, D>& sagg, T& mu, T& S) {
+    constexpr int MAT = D * D, SYM = Dim<D>::SYM;
+    T Q[SYM];
+    sym_from_full<T, D>(Qf, Q);
+    T mp[D], Pp[SYM], FP[MAT], u[D];
+    MeanCov<T, D> prev = s;
+    kf_step(s, F, Q, y, h, a.R, (k == 0) && a.seg_first, ll, mp, Pp, FP);
+    sym_vec<T, D, kPkStep>(Pp, h, u);
+    S = dot_add<T, D, kPkStep>(h, u, a.R);
+    mu = dot_add<T, D, kPkStep>(h, mp, T(0));
+    if (SMOOTH && k > k0) {                 // element of step k-1 from this step's predict
+        SmthElem<T, D> e, r;
+        smth_element(prev, mp, Pp, FP, e);
+        smth_combine(sagg, e, r);
+        sagg = r;
+    }
+}
+
+// mean and variance of f = H x under (m, P)
+template <typename T, int D>
+__device__ __forceinline__ void gp_project(const GpModel<T>& m, const MeanCov<T, D>& s, T& mu, T& var) {
+    mu = T(0);
+    var = T(0);
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+        mu += m.H[r] * s.m[r];
+#pragma unroll
+        for (int c = 0; c < D; ++c) var += m.H[r] * m.H[c] * s.P[symi<D>(r < c ? r : c, r < c ? c : r)];
+    }
+}
+
+// (m, v) the smoothed law of f_k given ALL observations, y its observation with noise variance R > 0: the law of y_k given
+// the others is N((m R - y v) / (R - v), R^2 / (R - v)) (v < R: the posterior of f_k is narrower than the factor it contains).
+// At a missing step nothing is left out: N(m, v + R), and no density.
+template <typename T>
+__device__ __forceinline__ void loo_step(T m, T v, T R, T y, T& mean, T& var, LogLik& lpd) {
+    if (is_nan(y)) {
+        mean = m;
+        var = v + R;
+        return;
+    }
+    const T c = R / (R - v);
+    mean = c * (m - y * (v / R));
+    var = c * R;
+    lpd.add(ll_diff(y, mean), ll_wide(var));
+}
+
+// ---------------------------------------------------------------------------------------------
 // reduce
 // ---------------------------------------------------------------------------------------------
 // LDS of the fused kernels: declared once per kernel and handed to the bodies, so that the one-launch kernel (below), which
@@ -157,8 +216,9 @@ __global__ __launch_bounds__(kBlock) void k_gp_reduce(const GpArgs<T> g) {
 // ---------------------------------------------------------------------------------------------
 // apply (+ log-likelihood, + smoothing aggregates when SMOOTH); fms / fPs are written when non-null
 // ---------------------------------------------------------------------------------------------
-template <typename T, int D, bool SMOOTH, bool NT, bool HET = false>
-__device__ __forceinline__ void gp_apply_body(const GpArgs<T>& g, GpLds<T, D>& sh, const T* rs = nullptr) {
+template <typename T, int D, bool SMOOTH, bool NT, bool HET = false, bool OSA = false>
+__device__ __forceinline__ void gp_apply_body(const GpArgs<T>& g, GpLds<T, D>& sh, const T* rs = nullptr,
+                                              const GpLooOut<T>& lo = GpLooOut<T>{}) {
     constexpr int MAT = D * D, SYM = Dim<D>::SYM, NF = Dim<D>::NFILT, G = 4;
     using FE = FiltElem<T, D>;
     using SE = SmthElem<T, D>;
@@ -228,7 +288,12 @@ __device__ __forceinline__ void gp_apply_body(const GpArgs<T>& g, GpLds<T, D>& s
             T F[MAT], Qf[MAT];
             lti_step<T, D>(g.m, t - tprev, F, Qf);
             tprev = t;
-            if constexpr (HET) gp_apply_step_r<T, D, SMOOTH>(a, k, k0, F, Qf, y, h, het_noise(a.R, rk, y), s, ll, sagg);
+            if constexpr (OSA) {
+                T mu, S;
+                gp_apply_step_osa<T, D, SMOOTH>(a, k, k0, F, Qf, y, h, s, ll, sagg, mu, S);
+                if (lo.osa_mean) lo.osa_mean[k] = mu;
+                if (lo.osa_var) lo.osa_var[k] = S;
+            } else if constexpr (HET) gp_apply_step_r<T, D, SMOOTH>(a, k, k0, F, Qf, y, h, het_noise(a.R, rk, y), s, ll, sagg);
             else filter_apply_step<T, D, SMOOTH>(a, k, k0, F, Qf, y, h, s, ll, sagg);
             if (store) {
                 T Pf[MAT];
@@ -348,8 +413,8 @@ static __global__ __launch_bounds__(kBlock) void k_gpb_finalize(const double* ll
 // ---------------------------------------------------------------------------------------------
 // smoother apply
 // ---------------------------------------------------------------------------------------------
-template <typename T, int D, bool NT, bool PROJ = false>
-__device__ __forceinline__ void gp_smooth_body(const GpArgs<T>& g, GpLds<T, D>& sh) {
+template <typename T, int D, bool NT, bool PROJ = false, bool LOO = false>
+__device__ __forceinline__ void gp_smooth_body(const GpArgs<T>& g, GpLds<T, D>& sh, const GpLooOut<T>& lo = GpLooOut<T>{}) {
     constexpr int MAT = D * D, SYM = Dim<D>::SYM, NS = Dim<D>::NSMTH, G = 4;
     using SE = SmthElem<T, D>;
     using MC = MeanCov<T, D>;
@@ -386,9 +451,12 @@ __device__ __forceinline__ void gp_smooth_body(const GpArgs<T>& g, GpLds<T, D>& 
         stage_issue<GM>(gM + (long)(S - 1) * GM::SEG, pitchM, rM);
     }
     T tnext = T(0), tcur = T(0);
+    [[maybe_unused]] T ycur = T(0);
+    [[maybe_unused]] LogLik lpd;
     if (k0 < k1) {
         tnext = (k1 < a.N) ? g.m.ts[k1] : T(0);
         tcur = g.m.ts[k1 - 1];
+        if constexpr (LOO) ycur = a.ys[k1 - 1];
     }
     MC s;
 #pragma unroll
@@ -430,22 +498,30 @@ __device__ __forceinline__ void gp_smooth_body(const GpArgs<T>& g, GpLds<T, D>& 
             }
             const T t = tcur;
             if (k > 0) tcur = g.m.ts[k - 1];
+            [[maybe_unused]] const T y = ycur;
+            if constexpr (LOO) {
+                if (k > k0) ycur = a.ys[k - 1];
+            }
             const bool last = (k == a.N - 1);
             T F[MAT], Qf[MAT];
             if (!last) lti_step<T, D>(g.m, tnext - t, F, Qf);
             smoother_apply_step<T, D>(F, Qf, mk, Pk, last, s);
             tnext = t;
+            if constexpr (LOO) {
+                // the leave-one-out law of y_k at every step; sms / sPs are not written
+                T m, v, mean, var;
+                gp_project<T, D>(g.m, s, m, v);
+                loo_step(m, v, a.R, y, mean, var, lpd);
+                if (lo.loo_mean) lo.loo_mean[k] = mean;
+                if (lo.loo_var) lo.loo_var[k] = var;
+                continue;
+            }
             if constexpr (PROJ) {
                 // posterior of f = H x at the query rows only (pssgp/model.py:107-111)
                 const int q = g.qslot[k];
                 if (q >= 0) {
-                    T mu = T(0), var = T(0);
-#pragma unroll
-                    for (int r = 0; r < D; ++r) {
-                        mu += g.m.H[r] * s.m[r];
-#pragma unroll
-                        for (int c = 0; c < D; ++c) var += g.m.H[r] * g.m.H[c] * s.P[symi<D>(r < c ? r : c, r < c ? c : r)];
-                    }
+                    T mu, var;
+                    gp_project<T, D>(g.m, s, mu, var);
                     g.pmean[q] = mu;
                     g.pvar[q] = var;
                 }
@@ -466,6 +542,10 @@ __device__ __forceinline__ void gp_smooth_body(const GpArgs<T>& g, GpLds<T, D>& 
                 store_rec<T, MAT>(a.sPs + k * MAT, Pf);
             }
         }
+    }
+    if constexpr (LOO) {
+        const double t = block_sum_double(lpd.value(), lds_ll);
+        if (threadIdx.x == 0) lo.lpd_part[blockIdx.x] = t;
     }
     if (blockIdx.x == 0 && a.ll != nullptr) {
         double v = 0.0;

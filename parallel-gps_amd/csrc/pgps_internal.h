@@ -353,6 +353,21 @@ int launch_gp_het(pgps_ctx* ctx, GpArgs<double> g, const double* rs);
 template <int D>
 int launch_gp_adj_het(pgps_ctx* ctx, GpArgs<double> g, const double* rs, double* out);
 
+// predictive checks of a fitted model against its own data on the fused path (pgps_loo_inst.hip; fp64, d <= 3):
+// what the OSA flavour of the Kalman pass and the LOO flavour of the smoother write
+template <typename T>
+struct GpLooOut {
+    T* osa_mean;            // (N,) H m_k^-: mean of y_k given the observations before it                [device], or null
+    T* osa_var;             // (N,) H P_k^- H^T + R: its variance                                        [device], or null
+    T* loo_mean;            // (N,) mean of y_k given all other observations                             [device], or null
+    T* loo_var;             // (N,) its variance (noise included)                                        [device], or null
+    double* lpd_part;       // (nblocks,) workgroup sums of log N(y_k | loo_mean, loo_var), observed steps [scratch: set by the launch]
+};
+// reduce / Kalman pass (OSA) / smoother (LOO) / finalize over g (g.s.fms, g.s.fPs set: the filtered moments the smoother
+// reads); sums[2] = {log-likelihood, sum of the leave-one-out log densities over the observed steps} [device]
+template <int D>
+int launch_gp_loo(pgps_ctx* ctx, GpArgs<double> g, GpLooOut<double> o, double* sums);
+
 // log-likelihood + gradient on the fused path (pgps_grad.hip); all array pointers device
 int launch_grad(pgps_ctx* ctx, long N, int d, int np, const double* model, const double* ts, double t0,
                 const double* ys, double* out_dev);

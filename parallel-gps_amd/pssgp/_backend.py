@@ -163,6 +163,10 @@ def _declare(lib):
                                                                      P, P, P, c_double, P, P, P, P]
             getattr(lib, f"pgps_gp_ll_grad_adj_het{dev}_f64").argtypes = [P, c_long, c_int, c_double, P, P, P, P, c_double, P,
                                                                          c_double, P, P, P]
+    if hasattr(lib, "pgps_gp_loo_f64"):                 # (absent from libraries built before the predictive checks)
+        for dev in ("", "_dev"):
+            getattr(lib, f"pgps_gp_loo{dev}_f64").argtypes = [P, c_long, c_int, c_double, P, P, P, P, c_double, P, P, c_double,
+                                                             P, P, P, P, P]
     return lib
 
 
@@ -854,6 +858,41 @@ def gp_ll_grad_adj_het(form, Pinf, H, R, ts, ys, rs, t0=0.0, device=0):
     _het_context(device).call("pgps_gp_ll_grad_adj_het_f64", c_long(ts_a.shape[0]), c_int(d), *model, c_double(float(R)),
                               _ptr(ts_a), c_double(float(t0)), _ptr(ys_a), _ptr(rs_a), _ptr(out))
     return split_grad_stats(out, d)
+
+
+def normal_log_density(y, mean, var):
+    """log N(y | mean, var) elementwise in fp64; NaN where y is."""
+    y, mean, var = (np.asarray(a, np.float64) for a in (y, mean, var))
+    return -0.5 * (np.log(2.0 * np.pi) + np.log(var) + (y - mean) ** 2 / var)
+
+
+def gp_loo(form, Pinf, H, R, ts, ys, t0=0.0, osa=True, loo=True, device=0):
+    """The predictive checks of a fitted model against its own data in one filter and one smoother pass over the N training
+    steps (pgps_gp_loo_f64; fp64, d <= 3, R > 0).  Returns a dict with "ll" (the log-likelihood) and "loo_lpd" (the sum over the
+    observed rows of the leave-one-out log densities); with `osa`: "osa_mean", "osa_var" (N,), the law of y_k given the
+    observations before it, and "osa_log_density"; with `loo`: "loo_mean", "loo_var", the law of y_k given all other
+    observations, and "loo_log_density".  Variances include R; a log density is NaN where ys is (formed here from
+    (ys, mean, var): the library stores none).  osa = loo = False: no per-step array is stored or copied back."""
+    ts_a = _prep(ts, np.float64, (-1,))
+    ys_a = _prep(ys, np.float64, (-1,))
+    N = ts_a.shape[0]
+    if ys_a.shape[0] != N:
+        raise ValueError(f"observations has {ys_a.shape[0]} rows, the series {N} steps")
+    d, model = _fused_model(form, Pinf, H)
+    out = {}
+    for want, name in ((osa, "osa"), (loo, "loo")):
+        for part in ("mean", "var"):
+            out[f"{name}_{part}"] = np.empty(N, np.float64) if want else None
+    sums = np.zeros(2, np.float64)
+    ctx = _require(get_context(device), "pgps_gp_loo_f64", "pgps_gp_loo_*")
+    ctx.call("pgps_gp_loo_f64", c_long(N), c_int(d), *model, c_double(float(R)), _ptr(ts_a), _ptr(ys_a), c_double(float(t0)),
+             _ptr(out["osa_mean"]), _ptr(out["osa_var"]), _ptr(out["loo_mean"]), _ptr(out["loo_var"]), _ptr(sums))
+    for want, name in ((osa, "osa"), (loo, "loo")):
+        if want:
+            out[f"{name}_log_density"] = normal_log_density(ys_a, out[f"{name}_mean"], out[f"{name}_var"])
+    out = {k: v for k, v in out.items() if v is not None}
+    out["ll"], out["loo_lpd"] = float(sums[0]), float(sums[1])
+    return out
 
 
 # state dimensions of the general-LTI device path: row-cooperative kernels up to 16 (batched evaluation only there),

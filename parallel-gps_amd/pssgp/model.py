@@ -16,6 +16,7 @@ import numpy as np
 from . import _backend, config
 from ._evaluation import _multi_output, _public_evaluation, _single_output_evaluation
 from .batches import ModelBatches
+from .checks import ModelChecks
 from .forms import ModelForms
 from .gradients import ModelGradients, mask_wrt
 from .kalman.parallel import pkf, pkfs
@@ -96,7 +97,7 @@ def _as_columns(data):
     return (ts[:, None] if ts.ndim == 1 else ts), (ys[:, None] if ys.ndim == 1 else ys)
 
 
-class StateSpaceGP(ModelForms, ModelGradients, ModelBatches):
+class StateSpaceGP(ModelForms, ModelGradients, ModelBatches, ModelChecks):
     """GP regression on one input (time) axis.  Y (N, 1) is the reference's model.
 
     THE FUSED ROUTE.  The evaluations below that name it run the fused HIP kernels on host arrays when: parallel=True, a single
