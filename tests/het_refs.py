@@ -38,15 +38,22 @@ def dense_het(spec, t, y, R, s, tq=None):
     return ll, A.T @ alpha, np.diag(O.dense_K(spec, tq, tq)) - np.sum(A * A, axis=0)
 
 
-def ss_het(sde, t, y, R, s, tq=None):
-    """The same from the state-space form: sequential Kalman filter (+ RTS smoother over the merged series) with R_k = R + s_k."""
+def merged(t, y, Rk, tq):
+    """(t, y, Rk, is-a-query) of the series the predict calls filter: the sorted queries merged into the training rows (a query
+    before a training row of the same time), y and Rk NaN at the query rows."""
+    t, y, Rk, tq = (np.asarray(a, np.float64).reshape(-1) for a in (t, y, Rk, tq))
+    nanq = np.full(tq.size, np.nan)
+    return O.merge_sorted(t, tq, (y, nanq), (Rk, nanq), (np.zeros(t.size, bool), np.ones(tq.size, bool)))
+
+
+def ss_het(sde, t, y, R, s, tq=None, ssm=None):
+    """The same from the state-space form: sequential Kalman filter (+ RTS smoother over the merged series) with R_k = R + s_k.
+    `ssm`: O.get_ssm(sde, t', .) of the series t' that is filtered (t, or t merged with tq), where the caller has it already."""
     t, y, s = (np.asarray(a, np.float64).reshape(-1) for a in (t, y, s))
     Rk = R + s
     if tq is not None:
-        tq = np.asarray(tq, np.float64).reshape(-1)
-        nanq = np.full(tq.size, np.nan)
-        t, y, Rk, isq = O.merge_sorted(t, tq, (y, nanq), (Rk, nanq), (np.zeros(t.size, bool), np.ones(tq.size, bool)))
-    P0, Fs, Qs, H, _ = O.get_ssm(sde, t, R)
+        t, y, Rk, isq = merged(t, y, Rk, tq)
+    P0, Fs, Qs, H, _ = O.get_ssm(sde, t, R) if ssm is None else ssm
     h = H.reshape(-1)
     n, d = t.size, h.size
     m, P, ll = np.zeros(d), P0.copy(), 0.0
@@ -89,6 +96,76 @@ def series(n, seed=0, missing=0.2, run=None):
     if run is not None:
         y[run[0]:run[0] + run[1]] = np.nan
     return t, y, s
+
+
+def spaced_series(n, spacing, seed=0):
+    """Sorted times with steps `spacing` (a scalar or (n,)) x U(0.5, 1.5): at spacing 0.05 thousands of rows span hundreds of
+    lengthscales, which series() -- n rows packed into [0, 1] -- never does.  Two slow sines plus noise of variance R + s, s
+    log-uniform over two decades [0.01, 1] x R, 20 % of the rows NaN."""
+    rng = np.random.RandomState(4000 + n + seed)
+    t = 0.05 + np.cumsum(spacing * rng.uniform(0.5, 1.5, n))
+    s = R * 10.0 ** rng.uniform(-2.0, 0.0, n)
+    y = np.sin(0.7 * t) + 0.5 * np.sin(0.13 * t + 1.0) + np.sqrt(R + s) * rng.randn(n)
+    y[rng.rand(n) < 0.2] = np.nan
+    y[n // 2] = 0.3
+    return t, y, s
+
+
+def workgroup_forgetting(sde, t, y, Rk, span, ssm=None):
+    """(blocks, 2): per block of `span` consecutive steps, log2 max |A| and log2 max |E| of the block's total in the parallel
+    scans -- what the device compares with 2^-120 before it takes a neighbour's record for the whole carry.
+      A  the product of (I - K_k h^T) F_k over the block, K_k the gains of a filter started at the block's first step with
+         P = 0: the derivative of the filtered mean at the block's end with respect to the mean handed to the block;
+      E  the product G_a G_a+1 ... of the RTS smoother's gains over the block (filter from the start of the series; the last
+         step of the series has no gain: E = 0 there, -inf here).
+    These are properties of the data.  The device's total of the FIRST block has A = 0 exactly instead (its first element
+    carries the prior), as its total of the last block has E = 0.
+    Both products are renormalised at every step, so hundreds of binades do not underflow.  Rk scalar or (n,); NaN rows of y
+    carry no observation."""
+    t, y = (np.asarray(a, np.float64).reshape(-1) for a in (t, y))
+    Rk = np.broadcast_to(np.asarray(Rk, np.float64), t.shape)
+    P0, Fs, Qs, H, _ = O.get_ssm(sde, t, 1.0) if ssm is None else ssm
+    h = H.reshape(-1)
+    n, d = t.size, h.size
+    seen = ~np.isnan(y)
+
+    def update(P, k):
+        """(I - K h^T, filtered P) of step k from its predicted P"""
+        if not seen[k]:
+            return np.eye(d), P
+        u = P @ h
+        S = float(h @ u) + Rk[k]
+        P = P - np.outer(u, u) / S
+        return np.eye(d) - np.outer(u / S, h), 0.5 * (P + P.T)
+
+    def scaled(M, log):
+        top = float(np.max(np.abs(M)))
+        return (M, -np.inf) if top == 0.0 else (M / top, log + math.log2(top))
+
+    G = np.zeros((n, d, d))
+    P = P0.copy()
+    for k in range(n):
+        if k > 0:
+            FP = Fs[k] @ P
+            pP = FP @ Fs[k].T + Qs[k]
+            G[k - 1] = np.linalg.solve(0.5 * (pP + pP.T), FP).T
+            P = 0.5 * (pP + pP.T)
+        else:
+            P = Fs[0] @ P @ Fs[0].T + Qs[0]
+        P = update(P, k)[1]
+    out = np.empty(((n + span - 1) // span, 2))
+    for b in range(out.shape[0]):
+        A, E, la, le = np.eye(d), np.eye(d), 0.0, 0.0
+        P = np.zeros((d, d))
+        for k in range(b * span, min(n, (b + 1) * span)):
+            P = Fs[k] @ P @ Fs[k].T + Qs[k]
+            IKh, P = update(0.5 * (P + P.T), k)
+            if la > -np.inf:
+                A, la = scaled(IKh @ Fs[k] @ A, la)
+            if le > -np.inf:
+                E, le = scaled(E @ G[k], le)
+        out[b] = la, le
+    return out
 
 
 def queries(t, k, seed=0):

@@ -25,12 +25,12 @@ def log_density(y, mean, var):
     return -0.5 * (LOG2PI + np.log(var) + (y - mean) ** 2 / var)
 
 
-def ss_checks(sde, t, y, Rk):
+def ss_checks(sde, t, y, Rk, ssm=None):
     """dict of FIELDS (N,), "osa_log_density", "loo_log_density" (NaN at the NaN rows of y), "ll", "loo_lpd" from the
-    state-space form; Rk scalar or (N,)."""
+    state-space form; Rk scalar or (N,).  `ssm`: O.get_ssm(sde, t, .) where the caller has it already."""
     t, y = (np.asarray(a, np.float64).reshape(-1) for a in (t, y))
     Rk = np.broadcast_to(np.asarray(Rk, np.float64), t.shape)
-    P0, Fs, Qs, H, _ = O.get_ssm(sde, t, 1.0)
+    P0, Fs, Qs, H, _ = O.get_ssm(sde, t, 1.0) if ssm is None else ssm
     h = H.reshape(-1)
     n, d = t.size, h.size
     m, P = np.zeros(d), P0.copy()

@@ -4,7 +4,8 @@ pgps_gp_ll_grad_adj_het_*): y_k = f(t_k) + e_k, e_k ~ N(0,
 (max norm relative to the largest entry), and dense conditioning with K + diag(R + s) at kernel_zoo's tolerance against the
 dense GP (1e-6).  Shapes: N in {1, 2, 37, 300} on the default geometry, 700 with one step per lane (three workgroups, a ragged
 tail, every wave of the block scan, the spine fold) and with three (a chunk that is no whole sub-tile); 20 % of y missing, s
-log-uniform over two decades."""
+log-uniform over two decades.  The LDS-staged road, eight steps per lane and the forgetting shortcut:
+test_gpu_fused_geometries.py."""
 import ctypes
 import functools
 

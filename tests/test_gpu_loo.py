@@ -5,7 +5,8 @@ filter + RTS smoother followed by the cavity formula at the project's 1e-9 (max 
 dense K_y^-1 formula over the observed rows at kernel_zoo's tolerance against the dense GP (1e-6).  Shapes: those of
 test_gpu_het_noise.py -- N in {1, 2, 37, 300} on the default geometry, 700 with one step per lane (three workgroups, a ragged
 tail, the spine fold, rows 252..260 missing across a workgroup boundary) and with three (a chunk that is no whole sub-tile: the
-unstaged path) -- and 300 rows with five repeated times (dt = 0; the references agree on it to 1e-9: test_loo_host.py)."""
+unstaged path) -- and 300 rows with five repeated times (dt = 0; the references agree on it to 1e-9: test_loo_host.py).
+The LDS-staged road, eight steps per lane and the forgetting shortcut: test_gpu_fused_geometries.py."""
 import ctypes
 
 import numpy as np
