@@ -4,57 +4,37 @@
 Runs on the host like the reference's (`tf.scan` on `/cpu:0`), through the C++ twins in
 libpgps.so (`pgps_seq_kf_* / pgps_seq_ks_*`, csrc/pgps_seq_host.cpp).
 """
-import ctypes
-
 import numpy as np
 
 from .. import _backend
 
 __all__ = ["kf", "ks", "kfs", "ks_sample", "sample_normals", "ks_cov"]
 
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-
-
-def _declare(lib):
-    if getattr(lib, "_pgps_seq_declared", False):
-        return
-    P, L, I = ctypes.c_void_p, ctypes.c_long, ctypes.c_int
-    for suf, real in (("f64", ctypes.c_double), ("f32", ctypes.c_float)):
-        getattr(lib, f"pgps_seq_kf_{suf}").argtypes = [L, I, P, P, P, P, real, P, P, P, P, P, P]
-        getattr(lib, f"pgps_seq_ks_{suf}").argtypes = [L, I, P, P, P, P, P, P, P]
-        if hasattr(lib, f"pgps_seq_kf_het_{suf}"):
-            getattr(lib, f"pgps_seq_kf_het_{suf}").argtypes = [L, I, P, P, P, P, P, P, P, P, P, P, P]
-    lib._pgps_seq_declared = True
+_ptr = _backend._ptr
 
 
 def kf(lgssm, observations, return_loglikelihood=False, return_predicted=False, observation_variances=None):
     """observation_variances (N,): the noise variance of EVERY step (pgps_seq_kf_het_*), in place of the model's R -- read
     where the observation is not NaN only.  None: the model's R at every step."""
     lib = _backend.load_library()
-    _declare(lib)
     dtype = _backend._dtype_of(lgssm)
-    suf, real = _backend._suffix(dtype)
+    suf, _ = _backend._suffix(dtype)
     P0, Fs, Qs, H, R, N, d = _backend._unpack_lgssm(lgssm, dtype)
     ys = _backend._prep(observations, dtype, (-1,))
     fms, fPs = np.empty((N, d), dtype), np.empty((N, d, d), dtype)
     mps = np.empty((N, d), dtype) if return_predicted else None
     Pps = np.empty((N, d, d), dtype) if return_predicted else None
-    ll = ctypes.c_double(0.0)
+    ll, llp = _backend._scalar_out()
     if observation_variances is not None:
-        Rs = _backend._prep(observation_variances, dtype, (-1,))
-        if Rs.shape[0] != N:
-            raise ValueError(f"observation_variances has {Rs.shape[0]} entries, the series {N} steps")
-        code = getattr(lib, f"pgps_seq_kf_het_{suf}")(N, d, _ptr(P0), _ptr(Fs), _ptr(Qs), _ptr(H), _ptr(Rs), _ptr(ys),
-                                                      _ptr(fms), _ptr(fPs), ctypes.cast(ctypes.byref(ll), ctypes.c_void_p),
-                                                      _ptr(mps), _ptr(Pps))
-        _backend.check(None, code, "pgps_seq_kf_het")
+        noise = _backend._prep(observation_variances, dtype, (-1,))
+        if noise.shape[0] != N:
+            raise ValueError(f"observation_variances has {noise.shape[0]} entries, the series {N} steps")
+        name, noise = "pgps_seq_kf_het", _ptr(noise)
     else:
-        code = getattr(lib, f"pgps_seq_kf_{suf}")(N, d, _ptr(P0), _ptr(Fs), _ptr(Qs), _ptr(H), real(R), _ptr(ys),
-                                                  _ptr(fms), _ptr(fPs), ctypes.cast(ctypes.byref(ll), ctypes.c_void_p),
-                                                  _ptr(mps), _ptr(Pps))
-        _backend.check(None, code, "pgps_seq_kf")
+        name, noise = "pgps_seq_kf", R
+    code = getattr(lib, f"{name}_{suf}")(N, d, _ptr(P0), _ptr(Fs), _ptr(Qs), _ptr(H), noise, _ptr(ys), _ptr(fms), _ptr(fPs), llp,
+                                         _ptr(mps), _ptr(Pps))
+    _backend.check(None, code, name)
     out = (fms, fPs)
     if return_loglikelihood:
         out += (np.asarray(ll.value, dtype=dtype),)
@@ -65,7 +45,6 @@ def kf(lgssm, observations, return_loglikelihood=False, return_predicted=False, 
 
 def ks(lgssm, ms, Ps, mps, Pps):
     lib = _backend.load_library()
-    _declare(lib)
     dtype = _backend._dtype_of(lgssm)
     suf, _ = _backend._suffix(dtype)
     Fs = _backend._prep(lgssm[1], dtype)

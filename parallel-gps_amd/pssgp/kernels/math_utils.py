@@ -25,17 +25,14 @@ def _native_balancing_diagonal(F, n_iter):
     """The same sweep in libpgps' host code (pgps_host_balance_f64; the reference compiles this loop with numba):
     None when the library is not built."""
     try:
-        import ctypes
         from .. import _backend
-        lib = _backend.load_library()
-        fn = lib.pgps_host_balance_f64
+        fn = _backend.load_library().pgps_host_balance_f64
     except Exception:
         return None
     Fc = np.ascontiguousarray(F, dtype=np.float64)
     scale = np.empty(Fc.shape[0], np.float64)
     with np.errstate(all="ignore"):
-        code = fn(ctypes.c_int(Fc.shape[0]), Fc.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(int(n_iter)),
-                  scale.ctypes.data_as(ctypes.c_void_p))
+        code = fn(Fc.shape[0], _backend._ptr(Fc), int(n_iter), _backend._ptr(scale))
     return scale if code == 0 else None
 
 

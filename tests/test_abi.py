@@ -19,13 +19,56 @@ def lib():
     return _backend.load_library()
 
 
-def test_every_declared_symbol_is_exported(lib):
+def _header_prototypes():
+    """[(return type, name, [parameter declarations])] of every function include/pgps.h declares."""
     hdr = open(os.path.join(ROOT, "include", "pgps.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    names = sorted(set(re.findall(r"\b(pgps_[a-z0-9_]+)\s*\(", hdr)))
+    hdr = re.sub(r"//[^\n]*", "", hdr)
+    found = re.findall(r"([A-Za-z_][A-Za-z0-9_ \*]*?)\b(pgps_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
+    return [(" ".join(ret.split()), name, [" ".join(p.split()) for p in params.split(",") if p.strip() not in ("", "void")])
+            for ret, name, params in found]
+
+
+def test_every_declared_symbol_is_exported(lib):
+    names = sorted({name for _, name, _ in _header_prototypes()})
     assert len(names) >= 35
     missing = [n for n in names if not hasattr(lib, n)]
     assert not missing, missing
+
+
+def test_declared_signatures_match_the_header(lib):
+    """The binding's one signature table against the prototypes of include/pgps.h: every function has argtypes of the
+    prototype's length, every scalar parameter maps to exactly its ctypes type (a `long n` declared c_int would truncate
+    the series length without a word), every pointer to a pointer type, and the string returns to c_char_p."""
+    scalars = {"int": ctypes.c_int, "long": ctypes.c_long, "double": ctypes.c_double, "float": ctypes.c_float,
+               "size_t": ctypes.c_size_t, "unsigned long long": ctypes.c_ulonglong}
+    pointer_types = (ctypes.c_void_p, ctypes.c_char_p)
+    protos = _header_prototypes()
+    assert len(protos) >= 160 and len({name for _, name, _ in protos}) == len(protos)
+    wrong = []
+    for ret, name, params in protos:
+        fn = getattr(lib, name)
+        if fn.argtypes is None or len(fn.argtypes) != len(params):
+            wrong.append(f"{name}: argtypes {fn.argtypes} for {len(params)} parameters")
+            continue
+        for k, (decl, got) in enumerate(zip(params, fn.argtypes)):
+            if "*" in decl:
+                ok = got in pointer_types or issubclass(got, ctypes._Pointer)
+            else:
+                base = " ".join(w for w in decl.split()[:-1] if w != "const")       # (the last word is the parameter's name)
+                assert base in scalars, (name, decl)
+                ok = got is scalars[base]
+            if not ok:
+                wrong.append(f"{name}: parameter {k} `{decl}` declared {got.__name__}")
+        if "char" in ret:
+            if fn.restype is not ctypes.c_char_p:
+                wrong.append(f"{name}: returns `{ret}`, restype {fn.restype}")
+        else:
+            assert ret == "int", (name, ret)
+            if fn.restype is not ctypes.c_int:
+                wrong.append(f"{name}: returns int, restype {fn.restype}")
+    assert not wrong, "\n".join(wrong)
+    assert sum("char" in ret for ret, _, _ in protos) == 3
 
 
 def test_version_and_strerror(lib):
