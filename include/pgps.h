@@ -785,6 +785,31 @@ int pgps_gp_ll_grad_multi_f64(pgps_ctx*, long N, int M, int d, double lam, const
 int pgps_gp_ll_grad_multi_dev_f64(pgps_ctx*, long N, int M, int d, double lam, const double* N1, const double* N2,
                                   const double* Pinf, const double* H, double R, const double* ts, const double* ys, double t0,
                                   double* out);
+/* Whitened columns and their Gram matrix (csrc/pgps_whiten.hip.h).  With K_y = K + R I = L L^T on the observed rows in time
+ * order, the standardised innovations of column c, w[k, c] = (ys[k, c] - mu_c[k]) / sqrt(S_k), are W = L^-1 ys: any quadratic
+ * form a^T K_y^-1 b over the training points is a dot product of whitened columns, and gram = W^T W = ys^T K_y^-1 ys.
+ *   w       (N, M)  row-major; 0.0 at the rows that are not observed
+ *   gram    (M, M)  symmetric, gram[i, j] and gram[j, i] equal bit for bit; 1 <= M <= 16 (more: PGPS_E_INVALID).  W stays in
+ *                   the context's scratch and never reaches the host
+ *   logdet          sum of log S_k over the observed steps = log |K_y|: shared by the columns
+ *   n_obs           number of observed steps
+ * The Kalman pass is the one of pgps_gp_ll_multi_* (same scans, same rounds under pgps_set_batch_scratch) with the store of w
+ * added; the Gram matrix is summed from per-workgroup partials in a fixed order (no floating-point atomics): results repeat
+ * bit for bit.  Rows of ys, the other errors and the _dev forms (device pointers for ts, ys, w, gram, logdet, n_obs; they
+ * return with the launches enqueued; all-or-none rows are a precondition) as above.  The host-array forms return
+ * PGPS_E_NUMERIC when logdet or an entry of w / gram is not finite. */
+int pgps_gp_whiten_multi_f64(pgps_ctx*, long N, int M, int d, double lam, const double* N1, const double* N2,
+                             const double* Pinf, const double* H, double R, const double* ts, const double* ys, double t0,
+                             double* w, double* logdet, long* n_obs);
+int pgps_gp_whiten_multi_dev_f64(pgps_ctx*, long N, int M, int d, double lam, const double* N1, const double* N2,
+                                 const double* Pinf, const double* H, double R, const double* ts, const double* ys, double t0,
+                                 double* w, double* logdet, long* n_obs);
+int pgps_gp_gram_multi_f64(pgps_ctx*, long N, int M, int d, double lam, const double* N1, const double* N2,
+                           const double* Pinf, const double* H, double R, const double* ts, const double* ys, double t0,
+                           double* gram, double* logdet, long* n_obs);
+int pgps_gp_gram_multi_dev_f64(pgps_ctx*, long N, int M, int d, double lam, const double* N1, const double* N2,
+                               const double* Pinf, const double* H, double R, const double* ts, const double* ys, double t0,
+                               double* gram, double* logdet, long* n_obs);
 
 #ifdef __cplusplus
 }

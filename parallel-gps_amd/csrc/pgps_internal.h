@@ -336,6 +336,21 @@ int launch_gp_multi(pgps_ctx* ctx, GpMultiArgs a, int predict, double* ll);
 // Geometry and rounds as launch_gp_multi
 template <int D>
 int launch_gp_multi_grad(pgps_ctx* ctx, GpMultiArgs a, double* out);
+// whitened columns and their Gram matrix (pgps_whiten.hip.h, pgps_whiten_inst.hip): what the whitening flavour of the Kalman
+// pass writes besides the scan scratch
+struct GpWhitenOut {
+    double* w;                  // (N, ldw) row-major standardised innovations, 0.0 at the steps that are not observed
+    long ldw;
+    int w_aligned;              // w starts on a 16-byte boundary
+    double* ldpart;             // (2, nblocks): every workgroup's sum of log S_k and its count of observed steps
+};
+constexpr int kGramMax = 16;            // columns of the Gram kernels
+constexpr int kGramSlab = 1024;         // rows of W per workgroup of k_gram_partial
+// a.N, a.M, a.m, a.R, a.ys set by the caller (training steps only); logdet, n_obs [device].  w (N, M) [device]: the whitened
+// columns are stored there; w null: they stay in scratch and gram (M, M) [device], M <= kGramMax, is formed from them.
+// Geometry and rounds as launch_gp_multi
+template <int D>
+int launch_gp_whiten(pgps_ctx* ctx, GpMultiArgs a, double* w, double* gram, double* logdet, long* n_obs);
 
 // merge of two sorted time arrays on the device + NaN marking of the query rows (pgps_core.hip)
 template <typename T>

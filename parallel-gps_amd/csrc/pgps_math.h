@@ -1382,10 +1382,12 @@ struct LogLikM {
     }
 };
 
-// kf_step for MC columns: mp (MC, D), Pp, FP are handed out for the smoothing element
+// kf_step for MC columns: mp (MC, D), Pp, FP are handed out for the smoothing element; at an observed step the innovations
+// r_out (MC) = y - mu and their shared variance *S_out as well (the whitening pass stores r / sqrt(S)), both untouched at a
+// step that is not observed
 template <typename T, int D, int MC>
 PGPS_HD void kf_step_m(MeanCovM<T, D, MC>& s, const T* F, const T* Q /*sym*/, const T* y /*MC*/, bool obs, const T* h, T R,
-                       bool first, LogLikM<MC>& ll, T (*mp)[D], T* Pp, T* FP) {
+                       bool first, LogLikM<MC>& ll, T (*mp)[D], T* Pp, T* FP, double* r_out /*MC*/, double* S_out) {
 #pragma unroll
     for (int c = 0; c < MC; ++c) mat_vec<T, D>(F, s.m[c], mp[c]);
     predict_cov<T, D>(F, s.P, Q, FP, Pp);
@@ -1400,6 +1402,9 @@ PGPS_HD void kf_step_m(MeanCovM<T, D, MC>& s, const T* F, const T* Q /*sym*/, co
 #pragma unroll
         for (int c = 0; c < MC; ++c) r[c] = ll_diff(y[c], mu[c]);
         ll.add(r, ll_wide(S));
+#pragma unroll
+        for (int c = 0; c < MC; ++c) r_out[c] = r[c];
+        *S_out = ll_wide(S);
     }
     if (first) {
         T u0[D];
@@ -1434,6 +1439,13 @@ PGPS_HD void kf_step_m(MeanCovM<T, D, MC>& s, const T* F, const T* Q /*sym*/, co
 #pragma unroll
         for (int i = 0; i < Dim<D>::SYM; ++i) s.P[i] = Pp[i];
     }
+}
+// ... for the callers that keep nothing of the innovations
+template <typename T, int D, int MC>
+PGPS_HD void kf_step_m(MeanCovM<T, D, MC>& s, const T* F, const T* Q /*sym*/, const T* y /*MC*/, bool obs, const T* h, T R,
+                       bool first, LogLikM<MC>& ll, T (*mp)[D], T* Pp, T* FP) {
+    double r[MC], S;
+    kf_step_m<T, D, MC>(s, F, Q, y, obs, h, R, first, ll, mp, Pp, FP, r, &S);
 }
 
 template <typename T, int D, int MC>

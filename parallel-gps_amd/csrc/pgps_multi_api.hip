@@ -1,7 +1,8 @@
 // pgps_multi_api.hip -- the multi-column entry points of the C ABI (include/pgps.h: pgps_gp_ll_multi_*,
-// pgps_gp_predict_multi_*, pgps_gp_ll_grad_multi_*): argument checks, the all-or-none check of the host forms, staging
+// pgps_gp_predict_multi_*, pgps_gp_ll_grad_multi_*, pgps_gp_whiten_multi_*, pgps_gp_gram_multi_*): argument checks, the all-or-none check of the host forms, staging
 // through the context's buffers, the merge of training and query times with the source ROW of every merged step as its
-// payload, dispatch to launch_gp_multi<d> (pgps_multi_inst.hip) and launch_gp_multi_grad<d> (pgps_multi_grad_inst.hip).
+// payload, dispatch to launch_gp_multi<d> (pgps_multi_inst.hip), launch_gp_multi_grad<d> (pgps_multi_grad_inst.hip) and
+// launch_gp_whiten<d> (pgps_whiten_inst.hip).
 #include "pgps_host.h"
 
 using namespace pgps;
@@ -56,6 +57,19 @@ static int gp_ll_grad_multi_dev(pgps_ctx* ctx, long N, int M, int d, double lam,
     a.m.t_prev = t0;
     RoctxRange range_("parallel_filter");
     return for_dim<1, 3>(d, [&](auto D) { return launch_gp_multi_grad<D()>(ctx, a, out); });
+}
+
+// w (N, M) or gram (M, M), the other null (launch_gp_whiten)
+static int gp_whiten_multi_dev(pgps_ctx* ctx, long N, int M, int d, double lam, const double* N1, const double* N2,
+                               const double* Pinf, const double* H, double R, const double* ts, const double* ys, double t0,
+                               double* w, double* gram, double* logdet, long* n_obs) {
+    GpMultiArgs a;
+    TRY(multi_args(ctx, N, M, d, lam, N1, N2, Pinf, H, R, ts, ys, &a));
+    if ((!w && !gram) || !logdet || !n_obs) return PGPS_E_INVALID;
+    if (gram && M > kGramMax) return PGPS_E_INVALID;
+    a.m.t_prev = t0;
+    RoctxRange range_("parallel_filter");
+    return for_dim<1, 3>(d, [&](auto D) { return launch_gp_whiten<D()>(ctx, a, w, gram, logdet, n_obs); });
 }
 
 static int gp_predict_multi_dev(pgps_ctx* ctx, long N, long K, int M, int d, double lam, const double* N1, const double* N2,
@@ -185,4 +199,59 @@ extern "C" int pgps_gp_ll_grad_multi_f64(pgps_ctx* ctx, long N, int M, int d, do
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t i = 0; i < nout; ++i) out[i] = outh[i];
     return ll_multi_result(M, outh.data(), nullptr);
+}
+
+// the host form of both: nout doubles of w or gram come back, with logdet and n_obs
+static int gp_whiten_multi_host(pgps_ctx* ctx, long N, int M, int d, double lam, const double* N1, const double* N2,
+                                const double* Pinf, const double* H, double R, const double* ts, const double* ys, double t0,
+                                bool want_gram, double* out, double* logdet, long* n_obs) {
+    GpMultiArgs chk;
+    TRY(multi_args(ctx, N, M, d, lam, N1, N2, Pinf, H, R, ts, ys, &chk));
+    if (!out || !logdet || !n_obs) return PGPS_E_INVALID;
+    if (want_gram && M > kGramMax) return PGPS_E_INVALID;
+    if (!rows_all_or_none(N, M, ys)) return PGPS_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nout = want_gram ? (size_t)M * M : (size_t)N * M;
+    double *dts, *dys, *dout, *dsum;
+    TRY(stage_in(ctx, ctx->st[10], ts, (size_t)N, &dts));
+    TRY(stage_in(ctx, ctx->st[4], ys, (size_t)N * M, &dys));
+    TRY(stage_in<double>(ctx, ctx->st[7], nullptr, nout, &dout));
+    TRY(stage_in<double>(ctx, ctx->st[9], nullptr, 2, &dsum));           // logdet | n_obs (a long: 8 bytes as well)
+    static_assert(sizeof(long) == sizeof(double), "n_obs shares the staging buffer of logdet");
+    long* dcnt = reinterpret_cast<long*>(dsum + 1);
+    TRY(gp_whiten_multi_dev(ctx, N, M, d, lam, N1, N2, Pinf, H, R, dts, dys, t0, want_gram ? nullptr : dout,
+                            want_gram ? dout : nullptr, dsum, dcnt));
+    TRY(stage_out(ctx, out, dout, nout));
+    TRY(stage_out(ctx, logdet, dsum, (size_t)1));
+    TRY(stage_out(ctx, n_obs, dcnt, (size_t)1));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    bool finite = std::isfinite(*logdet);
+    for (size_t i = 0; i < nout && finite; ++i) finite = std::isfinite(out[i]);
+    return finite ? PGPS_OK : PGPS_E_NUMERIC;
+}
+
+extern "C" int pgps_gp_whiten_multi_dev_f64(pgps_ctx* ctx, long N, int M, int d, double lam, const double* N1, const double* N2,
+                                            const double* Pinf, const double* H, double R, const double* ts, const double* ys,
+                                            double t0, double* w, double* logdet, long* n_obs) {
+    if (!w) return PGPS_E_INVALID;
+    return gp_whiten_multi_dev(ctx, N, M, d, lam, N1, N2, Pinf, H, R, ts, ys, t0, w, nullptr, logdet, n_obs);
+}
+
+extern "C" int pgps_gp_whiten_multi_f64(pgps_ctx* ctx, long N, int M, int d, double lam, const double* N1, const double* N2,
+                                        const double* Pinf, const double* H, double R, const double* ts, const double* ys,
+                                        double t0, double* w, double* logdet, long* n_obs) {
+    return gp_whiten_multi_host(ctx, N, M, d, lam, N1, N2, Pinf, H, R, ts, ys, t0, false, w, logdet, n_obs);
+}
+
+extern "C" int pgps_gp_gram_multi_dev_f64(pgps_ctx* ctx, long N, int M, int d, double lam, const double* N1, const double* N2,
+                                          const double* Pinf, const double* H, double R, const double* ts, const double* ys,
+                                          double t0, double* gram, double* logdet, long* n_obs) {
+    if (!gram) return PGPS_E_INVALID;
+    return gp_whiten_multi_dev(ctx, N, M, d, lam, N1, N2, Pinf, H, R, ts, ys, t0, nullptr, gram, logdet, n_obs);
+}
+
+extern "C" int pgps_gp_gram_multi_f64(pgps_ctx* ctx, long N, int M, int d, double lam, const double* N1, const double* N2,
+                                      const double* Pinf, const double* H, double R, const double* ts, const double* ys,
+                                      double t0, double* gram, double* logdet, long* n_obs) {
+    return gp_whiten_multi_host(ctx, N, M, d, lam, N1, N2, Pinf, H, R, ts, ys, t0, true, gram, logdet, n_obs);
 }

@@ -1,5 +1,7 @@
 """The fused path: discretisation inside the scan kernels (SDEs with F = -lam I + N, N nilpotent, d <= 3), and the
 forward-mode gradient calls of the same models and of their block-diagonal composites."""
+import ctypes
+
 import numpy as np
 
 from .arrays import _prep, _ptr, _scalar_out, _series_inputs, _suffix
@@ -106,6 +108,41 @@ def gp_ll_grad_multi(form, Pinf, H, R, ts, Y, t0=0.0, device=0):
     out = np.zeros(M + d * d + 2 * d + 1, np.float64)
     ctx.call("pgps_gp_ll_grad_multi_f64", N, M, d, *model, float(R), _ptr(ts_a), _ptr(Y_a), float(t0), _ptr(out))
     return split_grad_stats(out, d, M)
+
+
+GRAM_COLUMNS_MAX = 16           # pgps_gp_gram_multi_*: columns of V
+
+
+def _whiten_call(name, form, Pinf, H, R, ts, V, out, t0, device):
+    """pgps_gp_whiten_multi_f64 / pgps_gp_gram_multi_f64 on V (N, M): fills `out`, returns (logdet, n_obs)."""
+    ts_a, V_a, N = _series_inputs(ts, V, columns=True)
+    d, model = _fused_model(form, Pinf, H)
+    ctx = _require(get_context(device), name, "pgps_gp_whiten_multi_* / pgps_gp_gram_multi_*")
+    logdet, n_obs = ctypes.c_double(0.0), ctypes.c_long(0)
+    ctx.call(name, N, V_a.shape[1], d, *model, float(R), _ptr(ts_a), _ptr(V_a), float(t0), _ptr(out), ctypes.byref(logdet),
+             ctypes.byref(n_obs))
+    return float(logdet.value), int(n_obs.value)
+
+
+def gp_whiten_multi(form, Pinf, H, R, ts, V, t0=0.0, device=0):
+    """The whitened columns of V (N, M), any M >= 1, in one covariance pass (pgps_gp_whiten_multi_f64): W = L^-1 V with
+    K + R I = L L^T on the observed rows in time order -- the standardised innovations (V[k, c] - mu_c[k]) / sqrt(S_k) of the
+    Kalman pass, exact 0.0 at the rows that are not observed.  Returns (W (N, M), logdet = sum log S_k, n_obs).  Rows of V as
+    gp_ll_multi takes them."""
+    V = np.asarray(V, np.float64)
+    V = V[:, None] if V.ndim == 1 else V
+    W = np.empty(V.shape, np.float64)
+    return (W,) + _whiten_call("pgps_gp_whiten_multi_f64", form, Pinf, H, R, ts, V, W, t0, device)
+
+
+def gp_gram_multi(form, Pinf, H, R, ts, V, t0=0.0, device=0):
+    """G = W^T W = V^T (K + R I)^-1 V (M, M) for the M <= GRAM_COLUMNS_MAX columns of V (N, M), W as gp_whiten_multi returns
+    it but kept on the device (pgps_gp_gram_multi_f64): symmetric bit for bit, equal bits from call to call.  Returns
+    (G, logdet, n_obs).  More columns raise PgpsError (PGPS_E_INVALID)."""
+    V = np.asarray(V, np.float64)
+    V = V[:, None] if V.ndim == 1 else V
+    G = np.empty((V.shape[1], V.shape[1]), np.float64)
+    return (G,) + _whiten_call("pgps_gp_gram_multi_f64", form, Pinf, H, R, ts, V, G, t0, device)
 
 
 def _het_context(device):

@@ -73,6 +73,8 @@ _SIGNATURES = (
     ("pgps_gp_predict{dev}_{suf}", "PLLIDPPPPDPPDPPPP"),
     ("pgps_gp_ll_multi{dev}_f64 pgps_gp_ll_grad_multi{dev}_f64", "PLIIDPPPPDPPDP"),
     ("pgps_gp_predict_multi{dev}_f64", "PLLIIDPPPPDPPDPPPP"),
+    ("pgps_gp_whiten_multi_f64 pgps_gp_gram_multi_f64", "PLIIDPPPPDPPDPdl"),
+    ("pgps_gp_whiten_multi_dev_f64 pgps_gp_gram_multi_dev_f64", "PLIIDPPPPDPPDPPP"),
     ("pgps_gp_ll_het{dev}_f64", "PLIDPPPPDPPPDP"),
     ("pgps_gp_predict_het{dev}_f64", "PLLIDPPPPDPPPDPPPP"),
     ("pgps_gp_ll_grad_adj_het{dev}_f64", "PLIDPPPPDPDPPP"),

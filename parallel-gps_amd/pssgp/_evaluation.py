@@ -52,3 +52,26 @@ def _multi_output(route):
             return fn(self, *args, **kwargs)
         return wrapper
     return deco
+
+
+def _mean_function_route(route):
+    """A model with a mean_function answers this evaluation with its method `route` (trend.py: delegation to the zero-mean model
+    on the residuals); a model without one runs the decorated function exactly as before."""
+    def deco(fn):
+        @functools.wraps(fn)
+        def wrapper(self, *args, **kwargs):
+            if self._mean_function is not None:
+                return getattr(self, route)(*args, **kwargs)
+            return fn(self, *args, **kwargs)
+        return wrapper
+    return deco
+
+
+def _zero_mean_evaluation(fn):
+    """A public evaluation whose `thetas` layout has no place for the mean function's coefficients (the batches)."""
+    @functools.wraps(fn)
+    def wrapper(self, *args, **kwargs):
+        if self._mean_function is not None:
+            raise NotImplementedError(f"{fn.__name__} is not available with a mean_function set")
+        return fn(self, *args, **kwargs)
+    return wrapper

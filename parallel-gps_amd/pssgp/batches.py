@@ -7,7 +7,7 @@ import contextlib
 import numpy as np
 
 from . import _backend, config
-from ._evaluation import _single_output_evaluation
+from ._evaluation import _single_output_evaluation, _zero_mean_evaluation
 from .gradients import mask_wrt, matern_contract
 from .kernels import Matern12, Matern32, Matern52, RBF
 
@@ -84,6 +84,7 @@ class ModelBatches:
                 visit(b, form, F, P0, H)
         return thetas.shape[0]
 
+    @_zero_mean_evaluation
     @_single_output_evaluation
     def log_likelihood_batch(self, thetas):
         """Marginal log-likelihoods at B hyper-parameter settings in one call: `thetas` is (B, P) in the
@@ -151,6 +152,7 @@ class ModelBatches:
         mix = np.sum(w[:, None] * mean, axis=0)
         return mix, np.sum(w[:, None] * (var + (mean - mix[None, :]) ** 2), axis=0)
 
+    @_zero_mean_evaluation
     @_single_output_evaluation
     def predict_f_batch(self, Xnew, thetas, return_log_likelihood=False, reduce=None, weights=None):
         """predict_f at B hyper-parameter settings over the same series and query grid: `thetas` is (B, P) in the order of
@@ -344,6 +346,7 @@ class ModelBatches:
                 lls[b], grads[b] = self.log_likelihood_and_grad(wrt=wrt)
         return lls, grads
 
+    @_zero_mean_evaluation
     @_single_output_evaluation
     def log_likelihood_and_grad_batch(self, thetas, wrt=None):
         """(lls (B,), grads (B, P)): the marginal log-likelihood and its exact gradient at B hyper-parameter settings,

@@ -15,6 +15,7 @@ merge, no query rows, no refit.  predict_y / predict_log_density are GPflow's me
 import numpy as np
 
 from . import _backend, config
+from ._evaluation import _mean_function_route
 from .kalman import sequential
 
 
@@ -93,6 +94,7 @@ class ModelChecks:
         dtype = config.default_float()
         return tuple(out[f"{name}_{part}"][:, None].astype(dtype) for part in ("mean", "var", "log_density"))
 
+    @_mean_function_route("_trend_one_step_ahead")
     def one_step_ahead(self):
         """(mean, var, log_density), each (N, 1), in the order of the data rows: the law of y_k given the observations BEFORE
         it (in time), N(mean, var) with the noise in var, and log N(y_k | mean, var) -- the prequential predictive; the
@@ -104,6 +106,7 @@ class ModelChecks:
         self._single_output("one_step_ahead")
         return self._columns_of(self._checks(True, False), "osa")
 
+    @_mean_function_route("_trend_leave_one_out")
     def leave_one_out(self):
         """(mean, var, log_density), each (N, 1), in the order of the data rows: the law of y_k given ALL OTHER observations,
         N(mean, var) with the noise in var, and log N(y_k | mean, var) -- leave-one-out cross-validation without a refit.  At a
@@ -112,6 +115,7 @@ class ModelChecks:
         self._single_output("leave_one_out")
         return self._columns_of(self._checks(False, True), "loo")
 
+    @_mean_function_route("_trend_loo_lpd")
     def loo_log_predictive_density(self):
         """The leave-one-out cross-validation score (pseudo-likelihood): the sum of leave_one_out()'s log densities over the
         observed rows, a scalar.  On the fused route no per-step array is stored or copied back."""
@@ -129,6 +133,7 @@ class ModelChecks:
         mean, var = self.predict_f(Xnew)
         return mean, var + var.dtype.type(self.noise_variance)
 
+    @_mean_function_route("_trend_predict_log_density")
     def predict_log_density(self, data, full_cov=False, full_output_cov=False):
         """log N(Ynew | predict_y(Xnew)) for data = (Xnew, Ynew), (K, 1) (GPflow's predict_log_density): the score of
         held-out observations; NaN where Ynew is."""

@@ -9,12 +9,12 @@ the scan kernels) instead of TensorFlow autodiff.
 
 This module holds the model's data, the residency of its series on the device, the public evaluations and the routing
 between their paths; the kernel's device forms are forms.py's, the gradient methods gradients.py's, the batched
-evaluations batches.py's (mixins of the one class).
+evaluations batches.py's, the predictive checks checks.py's, the mean function's evaluations trend.py's (mixins of the one class).
 """
 import numpy as np
 
 from . import _backend, config
-from ._evaluation import _multi_output, _public_evaluation, _single_output_evaluation
+from ._evaluation import _mean_function_route, _multi_output, _public_evaluation, _single_output_evaluation
 from .batches import ModelBatches
 from .checks import ModelChecks
 from .forms import ModelForms
@@ -22,6 +22,7 @@ from .gradients import ModelGradients, mask_wrt
 from .kalman.parallel import pkf, pkfs
 from .kalman import sequential
 from .kalman.sequential import kf, kfs
+from .trend import ModelTrend
 
 
 def _merge_sorted(a, b, *args):
@@ -97,7 +98,7 @@ def _as_columns(data):
     return (ts[:, None] if ts.ndim == 1 else ts), (ys[:, None] if ys.ndim == 1 else ys)
 
 
-class StateSpaceGP(ModelForms, ModelGradients, ModelBatches, ModelChecks):
+class StateSpaceGP(ModelForms, ModelGradients, ModelBatches, ModelChecks, ModelTrend):
     """GP regression on one input (time) axis.  Y (N, 1) is the reference's model.
 
     THE FUSED ROUTE.  The evaluations below that name it run the fused HIP kernels on host arrays when: parallel=True, a single
@@ -122,11 +123,30 @@ class StateSpaceGP(ModelForms, ModelGradients, ModelBatches, ModelChecks):
     filter + smoother with a per-step variance (sequential.kf / kfs with observation_variances), any kernel, both modes --
     for maximum_log_likelihood_objective and predict_f; log_likelihood_and_grad (method None / "adjoint") exists on the
     fused route only.  predict_f(full_cov=True), the single-output evaluations above, gradient methods "dual" /
-    "differences", gradients of other kernels and Y with more than one column raise NotImplementedError."""
+    "differences", gradients of other kernels and Y with more than one column raise NotImplementedError.
 
-    def __init__(self, data, kernel, noise_variance=1.0, parallel=False, max_parallel=10000, observation_variances=None):
+    mean_function (pssgp.mean_functions: Constant, Linear, Polynomial, Basis; m(t) = Phi(t) beta with p explicit basis functions,
+    Rasmussen & Williams section 2.7): None (the default) is the zero-mean model, exactly -- no route, result or launch changes.
+    With one set, every single-output evaluation above has GPflow's meaning at the CURRENT beta: the GP models y - m(t)
+    (trend.py: delegation to one internal zero-mean model on the residuals; m added to returned means and draws and taken from
+    the y side of densities).  whiten(V) returns the standardised innovations W = L^-1 V of columns over the training points
+    (K + noise_variance I = L L^T), mean_gram() the Gram matrix G = V^T K_y^-1 V of V = [y, Phi] with logdet and the number of
+    observed rows; from G alone: mean_coefficients() (the GLS estimate, its covariance, the profile log-likelihood),
+    fit_mean_function(), log_marginal_likelihood_flat_mean() (R&W eq. 2.45), predict_f_gls() (eq. 2.41, 2.42: beta integrated out
+    under a flat prior) and the entries d ll / d beta = b - A beta that log_likelihood_and_grad() appends after noise_variance's
+    (trainable_parameters() lists them as (mean_function, "beta", j)).  The fused route: ONE covariance pass over the 1 + p
+    columns with the whitened columns kept on the device and one Gram pass (_backend.gp_gram_multi, 1 + p <= 16; whiten():
+    _backend.gp_whiten_multi, any number of columns; predict_f_gls: one _backend.gp_predict_multi call on [y, Phi]).
+    Everything else -- parallel=False, float32, other kernels, times out of order, more columns -- is the host twin: the
+    sequential filter's innovations column by column, any kernel.  Y with more than one column, observation_variances,
+    log_likelihood_batch, log_likelihood_and_grad_batch and predict_f_batch (their thetas layout has no place for beta) raise
+    NotImplementedError; a design matrix without full column rank on the observed rows raises ValueError."""
+
+    def __init__(self, data, kernel, noise_variance=1.0, parallel=False, max_parallel=10000, observation_variances=None,
+                 mean_function=None):
         self.noise_variance = float(noise_variance)
         self._obs_var = None
+        self._mean_function = None
         ts, ys = _as_columns(data)
         if ys.ndim != 2 or ys.shape[1] < 1:
             raise ValueError(f"observations must be (N,) or (N, M) with M >= 1, got shape {ys.shape}")
@@ -142,6 +162,7 @@ class StateSpaceGP(ModelForms, ModelGradients, ModelBatches, ModelChecks):
             self._kf = lambda ssm, y: pkf(ssm, y, return_loglikelihood=True, max_parallel=ts.shape[0])
             self._kfs = lambda ssm, y: pkfs(ssm, y, max_parallel=max_parallel)
         self.observation_variances = observation_variances
+        self.mean_function = mean_function
 
     @property
     def observation_variances(self):
@@ -150,6 +171,8 @@ class StateSpaceGP(ModelForms, ModelGradients, ModelBatches, ModelChecks):
 
     @observation_variances.setter
     def observation_variances(self, value):
+        if value is not None and self._mean_function is not None:
+            raise NotImplementedError("observation_variances is not available with a mean_function set")
         self._obs_var = None if value is None else self._checked_obs_var(value, self._data[1])
 
     def _checked_obs_var(self, value, ys):
@@ -389,6 +412,7 @@ class StateSpaceGP(ModelForms, ModelGradients, ModelBatches, ModelChecks):
         return config.default_float()(stats[0]), self._host_adjoint_grad(fused, stats, wrt)
 
     # -- the public evaluations ------------------------------------------------------------------------
+    @_mean_function_route("_trend_predict_f")
     @_multi_output("_multi_predict_f")
     @_public_evaluation
     def predict_f(self, Xnew, full_cov=False, full_output_cov=False):
@@ -497,6 +521,7 @@ class StateSpaceGP(ModelForms, ModelGradients, ModelBatches, ModelChecks):
             cov = sequential.ks_cov(ssm, fPs, sPs, rows, H=h)
         return mean[inverse][:, None].astype(dtype), cov[np.ix_(inverse, inverse)][None].astype(dtype)
 
+    @_mean_function_route("_trend_predict_f_samples")
     @_single_output_evaluation
     def predict_f_samples(self, Xnew, num_samples=None, full_cov=True, full_output_cov=False, seed=None):
         """Joint posterior draws of f at `Xnew` (GPflow's predict_f_samples): (S, K, 1), or (K, 1) when num_samples is
@@ -536,6 +561,7 @@ class StateSpaceGP(ModelForms, ModelGradients, ModelBatches, ModelChecks):
         out = f[:, :, None].astype(dtype)
         return out[0] if num_samples is None else out
 
+    @_mean_function_route("_trend_objective")
     @_multi_output("_multi_objective")
     @_public_evaluation
     def maximum_log_likelihood_objective(self):
@@ -567,8 +593,13 @@ class StateSpaceGP(ModelForms, ModelGradients, ModelBatches, ModelChecks):
         lengthscales, Periodic's period and its base kernel's parameters, the leaves of sums and products in order),
         then the observation-noise variance (pssgp/model.py:68)."""
         self._param_key()                           # (validates the memoised structure of the kernel)
-        return list(self._struct_memo[2]) + [(self, "noise_variance")]
+        params = list(self._struct_memo[2]) + [(self, "noise_variance")]
+        if self._mean_function is not None:
+            # ... then the mean function's coefficients, (owner, "beta", j): entries of one array
+            params += [(self._mean_function, "beta", j) for j in range(np.shape(self._mean_function.beta)[0])]
+        return params
 
+    @_mean_function_route("_trend_ll_and_grad")
     @_multi_output("_multi_ll_and_grad")
     @_public_evaluation
     def log_likelihood_and_grad(self, wrt=None, method=None):
