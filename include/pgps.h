@@ -615,6 +615,50 @@ int pgps_gp_loo_dev_f64(pgps_ctx*, long N, int d, double lam, const double* N1, 
                         const double* H, double R, const double* ts, const double* ys, double t0, double* osa_mean,
                         double* osa_var, double* loo_mean, double* loo_var, double* sums /* 2 */);
 
+/* ---- Laplace inference for non-Gaussian observations (fused path, fp64, d <= 3) -------------------------
+ * Observations y_k ~ p(y | f(t_k)) with a log-concave likelihood, `lik` one of PGPS_LIK_* with one parameter `par` (csrc/
+ * pgps_lik.h: lp = log p, g = lp', W = -lp'' floored at 1e-10, d3 = lp''').  A SITE formed at f is the Gaussian factor
+ * N(z | f, s), s = 1 / W, z = f + g / W; at a NaN row of ys, z = NaN and s = 1 (the filter skips the row).
+ *
+ * pgps_gp_newton_*: ONE Newton step of the mode search = one Gaussian smoothing pass over the sites (zs, ss) with R = 0 (the
+ * per-observation-noise reduce and Kalman pass as they are, a smoother that projects at EVERY training step, a finalize):
+ *   f_out      H x smoothed mean at every step = K (K + S)^-1 z, the new iterate;     v_out   its smoothed variance;
+ *   alpha_out  (zs - f_out) / ss = K^-1 f_out, 0 at the NaN rows;
+ *   zs_out, ss_out   the sites formed at f_out (what the next step takes as zs, ss);
+ *   sums[6]    [0] the Gaussian log-likelihood of (zs, ss)      [1] sum lp(ys | f_out)      [2] sum f_out alpha_out
+ *              [3] sum [lp - log N(zs_out | f_out, ss_out)]     [4] max |f_out - f_prev| over all steps (0 when f_prev is NULL)
+ *              [5] the number of observed steps.
+ * lp and [3] run over the observed steps.  The log of the Laplace evidence at a fixed point is [0] + [3] of consecutive passes.
+ * The outputs must not overlap zs, ss, f_prev.  Workgroup partials are added in index order and the maximum is exact in any
+ * order: equal calls give equal bits.  The smoothed states are not stored.  Four launches whatever N (pgps_set_chunk
+ * honoured; pgps_set_one_launch and pgps_set_resident do not apply).
+ *
+ * pgps_lik_sites_*: the elementwise start and the damped steps: f = f_a + step (f_b - f_a), alpha likewise (f_b NULL: f_a, alpha_a
+ * as they are), the sites at f, sums[3] = {sum lp, sum f alpha, sum [lp - log N(zs_out | f, ss_out)]}.  Outputs may be the
+ * inputs' own arrays.  Two launches.
+ *
+ * The _dev forms take device pointers for every array and for sums and are asynchronous on the context's stream; the host forms
+ * also check that ss is finite and > 0 wherever zs is observed (PGPS_E_INVALID) and return PGPS_E_NUMERIC on a non-finite sum.
+ * A null pointer (f_prev, f_b, alpha_b excepted), N < 1, lam <= 0, an unknown lik, a Gaussian or Poisson par that is not finite
+ * and > 0: PGPS_E_INVALID; d outside 1..3: PGPS_E_UNSUPPORTED_DIM. */
+#define PGPS_LIK_GAUSSIAN 0         /* y ~ N(f, par) */
+#define PGPS_LIK_BERNOULLI_LOGIT 1  /* y in {0, 1}, p(y = 1) = 1 / (1 + exp(-f)); par unused */
+#define PGPS_LIK_POISSON_EXP 2      /* y ~ Poisson(par exp(f)); lp leaves out -lgamma(y + 1) */
+int pgps_gp_newton_f64(pgps_ctx*, long N, int d, double lam, const double* N1, const double* N2, const double* Pinf,
+                       const double* H, int lik, double par, const double* ts, const double* ys, const double* zs,
+                       const double* ss, const double* f_prev /* may be NULL */, double t0, double* f_out, double* v_out,
+                       double* alpha_out, double* zs_out, double* ss_out, double* sums /* 6 */);
+int pgps_gp_newton_dev_f64(pgps_ctx*, long N, int d, double lam, const double* N1, const double* N2, const double* Pinf,
+                           const double* H, int lik, double par, const double* ts, const double* ys, const double* zs,
+                           const double* ss, const double* f_prev /* may be NULL */, double t0, double* f_out, double* v_out,
+                           double* alpha_out, double* zs_out, double* ss_out, double* sums /* 6 */);
+int pgps_lik_sites_f64(pgps_ctx*, long N, int lik, double par, const double* ys, const double* f_a, const double* alpha_a,
+                       const double* f_b /* may be NULL */, const double* alpha_b /* may be NULL */, double step, double* f_out,
+                       double* alpha_out, double* zs_out, double* ss_out, double* sums /* 3 */);
+int pgps_lik_sites_dev_f64(pgps_ctx*, long N, int lik, double par, const double* ys, const double* f_a, const double* alpha_a,
+                           const double* f_b /* may be NULL */, const double* alpha_b /* may be NULL */, double step,
+                           double* f_out, double* alpha_out, double* zs_out, double* ss_out, double* sums /* 3 */);
+
 /* ---- sequential mode: pssgp/kalman/sequential.py:11-73 (kf, ks) ------------------------
  * StateSpaceGP(parallel=False).  Host arithmetic on HOST pointers, as in the reference (its
  * sequential mode is the CPU `tf.scan`).  No context needed.  mps / Pps (predicted moments,

@@ -16,6 +16,7 @@
 #pragma once
 
 #include "pgps_kernels.hip.h"
+#include "pgps_lik.h"
 
 namespace pgps {
 
@@ -147,6 +148,63 @@ __device__ __forceinline__ void loo_step(T m, T v, T R, T y, T& mean, T& var, Lo
     mean = c * (m - y * (v / R));
     var = c * R;
     lpd.add(ll_diff(y, mean), ll_wide(var));
+}
+
+// ---------------------------------------------------------------------------------------------
+// one Newton step of a Laplace approximation: a compile-time flavour of the smoother, SITE, off by
+// default -- the other instantiations are what they were.  The pass smooths Gaussian sites N(z_k | f_k, s_k) (the Kalman pass
+// before it is the HET one over (zs, ss), R = 0); the smoother projects at every step as LOO does, and the epilogue site_step
+// forms alpha_k, evaluates the likelihood at the new f_k (pgps_lik.h), stores the new iterate and the sites formed at it, and
+// accumulates the pass's sums per lane; one set of partials per workgroup (GpSiteOut::part), summed afterwards in a fixed
+// order.  sms / sPs are not written.  Instantiated in pgps_site_inst.hip only.
+// ---------------------------------------------------------------------------------------------
+struct SiteAcc {
+    double lp = 0.0, fa = 0.0, corr = 0.0, dmax = 0.0, count = 0.0;
+};
+
+// a maximum that keeps a NaN once it has met one (fmax would drop it: a diverged iterate must not read as converged)
+__device__ __forceinline__ double max_nan(double a, double b) {
+    return (b > a || b != b) ? b : a;
+}
+
+// the workgroup's maximum (block_sum_double's shape: waves by shuffles, then one LDS word per wave)
+__device__ __forceinline__ double block_max_nan(double x, double* lds) {
+#pragma unroll
+    for (int s = kWave / 2; s > 0; s >>= 1) x = max_nan(x, __shfl_down(x, s, kWave));
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x / kWave;
+    if (lane == 0) lds[wave] = x;
+    __syncthreads();
+    double t = lds[0];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) t = max_nan(t, lds[w]);
+    __syncthreads();
+    return t;
+}
+
+// (f, v) the smoothed law of f_k; (z, s) the site the pass used there (z NaN: none); y the observation; fp the iterate the site
+// was formed at
+template <typename T>
+__device__ __forceinline__ void site_step(const GpSiteOut<T>& so, long k, T f, T v, T z, T s, T y, T fp, bool have_prev,
+                                          SiteAcc& acc) {
+    const double fd = double(f);
+    const double alpha = is_nan(z) ? 0.0 : (double(z) - fd) / double(s);
+    double z_new = double(y), s_new = 1.0;           // (y is NaN at a missing row)
+    if (!is_nan(y)) {
+        const LikSite ls = lik_site(so.lik, so.par, double(y), fd);
+        z_new = ls.z;
+        s_new = ls.s;
+        acc.lp += ls.lp;
+        acc.corr += ls.corr;
+        acc.count += 1.0;
+    }
+    acc.fa += fd * alpha;
+    if (have_prev) acc.dmax = max_nan(acc.dmax, fabs(fd - double(fp)));
+    so.f_out[k] = f;
+    so.v_out[k] = v;
+    so.alpha_out[k] = T(alpha);
+    so.zs_out[k] = T(z_new);
+    so.ss_out[k] = T(s_new);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -413,8 +471,9 @@ static __global__ __launch_bounds__(kBlock) void k_gpb_finalize(const double* ll
 // ---------------------------------------------------------------------------------------------
 // smoother apply
 // ---------------------------------------------------------------------------------------------
-template <typename T, int D, bool NT, bool PROJ = false, bool LOO = false>
-__device__ __forceinline__ void gp_smooth_body(const GpArgs<T>& g, GpLds<T, D>& sh, const GpLooOut<T>& lo = GpLooOut<T>{}) {
+template <typename T, int D, bool NT, bool PROJ = false, bool LOO = false, bool SITE = false>
+__device__ __forceinline__ void gp_smooth_body(const GpArgs<T>& g, GpLds<T, D>& sh, const GpLooOut<T>& lo = GpLooOut<T>{},
+                                               const GpSiteOut<T>& so = GpSiteOut<T>{}) {
     constexpr int MAT = D * D, SYM = Dim<D>::SYM, NS = Dim<D>::NSMTH, G = 4;
     using SE = SmthElem<T, D>;
     using MC = MeanCov<T, D>;
@@ -453,10 +512,20 @@ __device__ __forceinline__ void gp_smooth_body(const GpArgs<T>& g, GpLds<T, D>& 
     T tnext = T(0), tcur = T(0);
     [[maybe_unused]] T ycur = T(0);
     [[maybe_unused]] LogLik lpd;
+    // SITE: the step's site (a.ys = zs, so.ss), its observation and the previous iterate, loaded a step ahead as ycur is
+    [[maybe_unused]] T scur = T(0), ocur = T(0), pcur = T(0);
+    [[maybe_unused]] SiteAcc sacc;
+    [[maybe_unused]] bool have_prev = false;
+    if constexpr (SITE) have_prev = so.f_prev != nullptr;
     if (k0 < k1) {
         tnext = (k1 < a.N) ? g.m.ts[k1] : T(0);
         tcur = g.m.ts[k1 - 1];
-        if constexpr (LOO) ycur = a.ys[k1 - 1];
+        if constexpr (LOO || SITE) ycur = a.ys[k1 - 1];
+        if constexpr (SITE) {
+            scur = so.ss[k1 - 1];
+            ocur = so.ys[k1 - 1];
+            if (have_prev) pcur = so.f_prev[k1 - 1];
+        }
     }
     MC s;
 #pragma unroll
@@ -499,8 +568,16 @@ __device__ __forceinline__ void gp_smooth_body(const GpArgs<T>& g, GpLds<T, D>& 
             const T t = tcur;
             if (k > 0) tcur = g.m.ts[k - 1];
             [[maybe_unused]] const T y = ycur;
-            if constexpr (LOO) {
+            if constexpr (LOO || SITE) {
                 if (k > k0) ycur = a.ys[k - 1];
+            }
+            [[maybe_unused]] const T sk = scur, ok = ocur, pk = pcur;
+            if constexpr (SITE) {
+                if (k > k0) {
+                    scur = so.ss[k - 1];
+                    ocur = so.ys[k - 1];
+                    if (have_prev) pcur = so.f_prev[k - 1];
+                }
             }
             const bool last = (k == a.N - 1);
             T F[MAT], Qf[MAT];
@@ -514,6 +591,13 @@ __device__ __forceinline__ void gp_smooth_body(const GpArgs<T>& g, GpLds<T, D>& 
                 loo_step(m, v, a.R, y, mean, var, lpd);
                 if (lo.loo_mean) lo.loo_mean[k] = mean;
                 if (lo.loo_var) lo.loo_var[k] = var;
+                continue;
+            }
+            if constexpr (SITE) {
+                // the new iterate and the sites formed at it, at every step; sms / sPs are not written
+                T m, v;
+                gp_project<T, D>(g.m, s, m, v);
+                site_step(so, k, m, v, y, sk, ok, pk, have_prev, sacc);
                 continue;
             }
             if constexpr (PROJ) {
@@ -546,6 +630,17 @@ __device__ __forceinline__ void gp_smooth_body(const GpArgs<T>& g, GpLds<T, D>& 
     if constexpr (LOO) {
         const double t = block_sum_double(lpd.value(), lds_ll);
         if (threadIdx.x == 0) lo.lpd_part[blockIdx.x] = t;
+    }
+    if constexpr (SITE) {
+        const double vals[4] = {sacc.lp, sacc.fa, sacc.corr, sacc.count};
+        const int slot[4] = {0, 1, 2, 4};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const double t = block_sum_double(vals[i], lds_ll);
+            if (threadIdx.x == 0) so.part[(long)slot[i] * a.nblocks + blockIdx.x] = t;
+        }
+        const double mx = block_max_nan(sacc.dmax, lds_ll);
+        if (threadIdx.x == 0) so.part[3L * a.nblocks + blockIdx.x] = mx;
     }
     if (blockIdx.x == 0 && a.ll != nullptr) {
         double v = 0.0;

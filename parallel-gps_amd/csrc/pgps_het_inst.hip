@@ -8,6 +8,7 @@
 // k_gp_smooth itself.  Three-launch forms only: reduce / Kalman pass / smoother with projection, and reduce / adjoint forward /
 // adjoint backward (+ the finalize of the partials); no one-workgroup form, no resident launch, no streaming stores.
 #include "pgps_gpadj.hip.h"
+#include "pgps_het.hip.h"
 #include "pgps_scratch.h"
 
 #ifndef PGPS_HET_D
@@ -16,27 +17,11 @@
 
 namespace pgps {
 
-struct GpHetArgs {
-    GpArgs<double> g;
-    const double* rs;       // (N,) per-step variances added to g.s.R; read at observed steps only      [device]
-};
-
+// (GpHetArgs, k_gph_reduce, k_gph_apply: pgps_het.hip.h)
 struct GpHetAdjArgs {
     GpAdjArgs ga;
     const double* rs;
 };
-
-template <int D>
-__global__ __launch_bounds__(kBlock) void k_gph_reduce(const GpHetArgs h) {
-    __shared__ double lds[kWaves * Dim<D>::NFILT];
-    gp_reduce_body<double, D, true>(h.g, lds, h.rs);
-}
-
-template <int D, bool SMOOTH>
-__global__ __launch_bounds__(kBlock) void k_gph_apply(const GpHetArgs h) {
-    __shared__ GpLds<double, D> sh;
-    gp_apply_body<double, D, SMOOTH, false, true>(h.g, sh, h.rs);
-}
 
 template <int D>
 __global__ __launch_bounds__(kBlock) void k_gph_gfwd(const GpHetAdjArgs h) {

@@ -383,6 +383,40 @@ struct GpLooOut {
 template <int D>
 int launch_gp_loo(pgps_ctx* ctx, GpArgs<double> g, GpLooOut<double> o, double* sums);
 
+// One Newton step of a Laplace approximation on the fused path (pgps_site_inst.hip; fp64, d <= 3): what the SITE
+// flavour of the smoother reads besides the sites' means (g.s.ys) and writes.  All arrays (N,) [device]
+template <typename T>
+struct GpSiteOut {
+    int lik;                // PGPS_LIK_*
+    double par;             // its parameter
+    const T* ys;            // the observations, NaN = missing (g.s.ys holds the sites' means zs, NaN at the same rows)
+    const T* ss;            // the sites' variances of this pass
+    const T* f_prev;        // the iterate the sites were formed at, or null
+    T* f_out;               // smoothed mean of f_k = H x_k: the new iterate
+    T* v_out;               // its smoothed variance
+    T* alpha_out;           // (zs - f_out) / ss, 0 at the missing rows
+    T* zs_out;              // the sites formed at f_out: means (NaN at the missing rows) ...
+    T* ss_out;              // ... and variances (1 at the missing rows)
+    double* part;           // (kSiteParts, nblocks) workgroup partials                                    [scratch: set by the launch]
+};
+constexpr int kSiteParts = 5;       // sum lp | sum f alpha | sum [lp - log N(z | f, s)] | max |f - f_prev| | observed steps
+// reduce / Kalman pass (both of the per-observation-noise flavour, on (g.s.ys, o.ss) with g.s.R = 0) / smoother (SITE) /
+// finalize; g.s.fms, g.s.fPs set; sums[6] [device] as pgps_gp_newton_dev_f64 documents them
+template <int D>
+int launch_gp_newton(pgps_ctx* ctx, GpArgs<double> g, GpSiteOut<double> o, double* sums);
+// the sites at f = f_a + step (f_b - f_a) (f_b null: f_a), elementwise, and sums[3] [device] (pgps_site_inst.hip, the d = 1 unit)
+struct LikSitesArgs {
+    long N;
+    int lik;
+    double par;
+    const double *ys, *f_a, *alpha_a, *f_b, *alpha_b;
+    double step;
+    double *f_out, *alpha_out, *zs_out, *ss_out;
+    double* part;           // (3, nblocks) workgroup partials                                             [scratch: set by the launch]
+    int nblocks;
+};
+int launch_lik_sites(pgps_ctx* ctx, LikSitesArgs a, double* sums);
+
 // log-likelihood + gradient on the fused path (pgps_grad.hip); all array pointers device
 int launch_grad(pgps_ctx* ctx, long N, int d, int np, const double* model, const double* ts, double t0,
                 const double* ys, double* out_dev);

@@ -79,6 +79,8 @@ _SIGNATURES = (
     ("pgps_gp_predict_het{dev}_f64", "PLLIDPPPPDPPPDPPPP"),
     ("pgps_gp_ll_grad_adj_het{dev}_f64", "PLIDPPPPDPDPPP"),
     ("pgps_gp_loo{dev}_f64", "PLIDPPPPDPPDPPPPP"),
+    ("pgps_gp_newton{dev}_f64", "PLIDPPPPIDPPPPPDPPPPPP"),
+    ("pgps_lik_sites{dev}_f64", "PLIDPPPPPDPPPPP"),
     ("pgps_gp_ll_grad{dev}_f64", "PLIIPPDPP"),
     ("pgps_gp_ll_grad_blocks{dev}_f64", "PLIIPIPPDPP"),
     ("pgps_gp_ll_grad_adj_dev_f64", "PLIDPPPPDPDPP"),
