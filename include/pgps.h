@@ -362,6 +362,19 @@ int pgps_lti_predict_f64(pgps_ctx*, long N, long K, int d, const double* F, cons
 int pgps_lti_predict_dev_f64(pgps_ctx*, long N, long K, int d, const double* F, const double* Pinf, const double* H,
                              double R, const double* ts, const double* ys, double t0, const double* tq, double* mean,
                              double* var, double* ll);
+/* linear functionals of the state (additive components of a sum kernel, derivatives of f: DESIGN.md 4z)
+ * as pgps_lti_predict_*: merge, missing observations at the query rows, discretise, filter + smoother over N + K steps;
+ * C (J,d) HOST, 1 <= J <= PGPS_MAX_FUNCTIONALS (else PGPS_E_INVALID); mean (K,J) = C sm, cov (K,J,J) = C sP C^T of
+ * query k, each (J,J) block symmetric bit for bit; ll nullable.  H stays the observation row.  2 <= d <= PGPS_MAX_DIM.
+ * d <= 16: 8 K J^2 <= 0x7fff0000 bytes, i.e. K J^2 <= 268427264 = 2^28 - 2^13 (the smoother addresses its outputs with
+ * 32-bit byte offsets inside one buffer descriptor; else PGPS_E_INVALID). */
+#define PGPS_MAX_FUNCTIONALS 8
+int pgps_lti_predict_lin_f64(pgps_ctx*, long N, long K, int d, int J, const double* F, const double* Pinf, const double* H,
+                             const double* C, double R, const double* ts, const double* ys, double t0, const double* tq,
+                             double* mean, double* cov, double* ll);
+int pgps_lti_predict_lin_dev_f64(pgps_ctx*, long N, long K, int d, int J, const double* F, const double* Pinf,
+                                 const double* H, const double* C, double R, const double* ts, const double* ys, double t0,
+                                 const double* tq, double* mean, double* cov, double* ll);
 /* model-level sampler, as pgps_lti_predict_*: merge sorted ts / tq (its query slots give the output column), missing
  * observations at the query rows, discretise, filter, sample; out (S,K) = H x at the K queries of samples s0..s0+S-1
  * (the library's draws under seed); ll (nullable) = training log-likelihood.  1 <= d <= PGPS_MAX_DIM_LANE, fp64. */

@@ -181,7 +181,15 @@ int merged_front(pgps_ctx* ctx, DevBuf* b, long N, long K, const T* ts, const T*
 
 // general LTI models (pgps_lti_api.hip)
 // the small model [F | Pinf | H] from host memory into ctx->lti[0], in one copy
-int lti_model_in(pgps_ctx* ctx, int d, const double* F, const double* Pinf, const double* H, double** model);
+// (with C: the J rows of the functionals follow, [F | Pinf | H | C], the same copy)
+int lti_model_in(pgps_ctx* ctx, int d, const double* F, const double* Pinf, const double* H, double** model,
+                 const double* C = nullptr, int J = 0);
+// the functionals of a pgps_lti_predict_lin_* call: C (J, d) HOST; lti_core then writes mean (K, J) and cov (K, J, J) [device]
+struct LtiLin {
+    const double* C;
+    int J;
+    double* cov;
+};
 // The array-path front of a model-level call over m (merged) steps: model in, Fs / Qs / fPs / fms (with `smooth`: sPs / sms
 // too) in ctx->lti[4..9], discretisation, then the filter (or filter + smoother).  ll [device] may be null.
 struct LtiFront {
@@ -191,7 +199,7 @@ struct LtiFront {
 int lti_filter_front(pgps_ctx* ctx, size_t m, int d, const double* F, const double* Pinf, const double* H, double R,
                      const double* ts_m, const double* ys_m, double t0, bool smooth, double* ll, LtiFront* o);
 int lti_core(pgps_ctx* ctx, size_t m, int d, const double* F, const double* Pinf, const double* H, double R, const double* ts_m,
-             const double* ys_m, double t0, const int* qslot, double* mean, double* var, double* ll);
+             const double* ys_m, double t0, const int* qslot, double* mean, double* var, double* ll, const LtiLin* lin = nullptr);
 int lti_ll_batch_dev(pgps_ctx* ctx, int B, long N, int d, const double* models, const double* ts, const double* ys, double t0,
                      double* ll);
 int lti_grad_dev(pgps_ctx* ctx, long N, int d, const double* F, const double* Pinf, const double* H, double R, const double* ts,

@@ -512,8 +512,10 @@ int launch_scan_rc(pgps_ctx* ctx, ScanArgs<Real> a, int d, Mode mode);
 // the same with nothing written per step: MODE_PKF = log-likelihood only; MODE_PKFS = H sm, H sP H^T at the steps
 // qslot marks (a.sPs / a.sms are then scratch of N d^2 / N d doubles for the smoothing elements)
 // (MODE_PKF with a.Qs == nullptr: implicit process noise Q_k = P0 - F_k P0 F_k^T, P0 must be stationary)
+// nfun > 0 (MODE_PKFS): the functionals flavour -- pmean (K, nfun) = C sm, pcov (K, nfun, nfun) = C sP C^T for C (nfun, d)
+// [device], pvar unused; same chain length as the plain projection
 int launch_scan_rc_proj(pgps_ctx* ctx, ScanArgs<double> a, int d, Mode mode, const int* qslot, double* pmean,
-                        double* pvar);
+                        double* pvar, int nfun = 0, const double* C = nullptr, double* pcov = nullptr);
 int launch_disc_rc(pgps_ctx* ctx, long N, int d, const double* F, const double* Pinf, const double* ts, double t0,
                    double* Fs, double* Qs, int batch = 1, long bs_model = 0);
 // log-likelihoods of `batch` models over one series: table = batch x [F | Pinf | H | R] (stride bs_model, device),
@@ -562,6 +564,11 @@ struct RcArgsT {
     Real *pmean, *pvar;       // (K,) H sm and H sP H^T at the query steps
     int dform;                  // the chains' smoothing totals are in innovation form (rc_apply1 DFORM): rc_smooth1 adds the filtered moments
     int quad;                   // level-1 kernels of the quad-cooperative family (pgps_qc.hip.h: fp32, 5 <= d <= 8, 16 chains per wave)
+    // functionals flavour of the projected-posterior mode (pgps_lti_predict_lin_*, fp64; nfun = 0 otherwise): pmean (K, nfun)
+    // = C sm, pcov (K, nfun, nfun) = C sP C^T at the query steps; pvar is not written
+    int nfun;                   // rows of C, 1 .. PGPS_MAX_FUNCTIONALS
+    const Real* C;              // (nfun, d)
+    Real* pcov;
 };
 using RcArgs = RcArgsT<double>;
 // defined in pgps_rc_inst.hip, one explicit instantiation per (scalar type, d)

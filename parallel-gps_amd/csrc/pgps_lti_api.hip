@@ -33,6 +33,62 @@ __global__ void k_project_rows(long m, int d, const int* __restrict__ qslot, con
     var[q] = v;
 }
 
+// ... and its J-row sibling (pgps_lti_predict_lin_*): C sm (J) and C sP C^T (J, J) at the query rows, one thread per merged
+// step.  One pass over the rows of sP: t_j = sP[a, :] c_j, then M[i][j] += c_i[a] t_j for i <= j; the mirror is a copy, so
+// the block is symmetric bit for bit.  The loops over the functionals have compile-time bounds (the J x J accumulators stay
+// in registers) and uniform guards; the rows of C are wave-uniform loads.
+__global__ void k_project_rows_lin(long m, int d, int J, const int* __restrict__ qslot, const double* __restrict__ C,
+                                   const double* __restrict__ sms, const double* __restrict__ sPs, double* __restrict__ mean,
+                                   double* __restrict__ cov) {
+    constexpr int JM = PGPS_MAX_FUNCTIONALS;
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m) return;
+    const int q = qslot[k];
+    if (q < 0) return;
+    const double* sm = sms + k * d;
+    const double* sP = sPs + k * (long)d * d;
+    double mu[JM], M[JM][JM];
+#pragma unroll
+    for (int i = 0; i < JM; ++i) {
+        mu[i] = 0.0;
+#pragma unroll
+        for (int j = 0; j < JM; ++j) M[i][j] = 0.0;
+    }
+    for (int a = 0; a < d; ++a) {
+        double t[JM];
+#pragma unroll
+        for (int j = 0; j < JM; ++j) t[j] = 0.0;
+        for (int b = 0; b < d; ++b) {
+            const double p = sP[(long)a * d + b];
+#pragma unroll
+            for (int j = 0; j < JM; ++j)
+                if (j < J) t[j] += p * C[j * d + b];
+        }
+        const double s = sm[a];
+#pragma unroll
+        for (int i = 0; i < JM; ++i) {
+            if (i < J) {
+                const double ci = C[i * d + a];
+                mu[i] += ci * s;
+#pragma unroll
+                for (int j = i; j < JM; ++j)
+                    if (j < J) M[i][j] += ci * t[j];
+            }
+        }
+    }
+    double* mq = mean + (long)q * J;
+    double* cq = cov + (long)q * J * J;
+#pragma unroll
+    for (int i = 0; i < JM; ++i) {
+        if (i < J) {
+            mq[i] = mu[i];
+#pragma unroll
+            for (int j = i; j < JM; ++j)
+                if (j < J) { cq[i * J + j] = M[i][j]; cq[j * J + i] = M[i][j]; }
+        }
+    }
+}
+
 // Fs / Qs of a block-diagonal model from the per-block results: element (i, j) of block step k goes to
 // (idx[i], idx[j]) of the big step k (the big arrays are zero elsewhere)
 // (blockIdx.y = one of several blocks of the same size: their model records -- [F_b | P_b | indices] -- lie `mstride` doubles
@@ -172,7 +228,7 @@ static int lti_disc_wc(pgps_ctx* ctx, size_t m, int d, const double* model, cons
 
 static int lti_dev_wc(pgps_ctx* ctx, size_t m, int d, const double* model, const double* F_host, const double* P_host,
                       double R, const double* ts_m, const double* ys_m, double t0, const int* qslot, double* mean,
-                      double* var, double* ll) {
+                      double* var, double* ll, const LtiLin* lin) {
     const size_t dd = (size_t)d * d;
     double *Fs, *Qs, *fms, *fPs;
     TRY(lti_disc_wc(ctx, m, d, model, F_host, P_host, ts_m, t0, &Fs, &Qs));
@@ -191,6 +247,12 @@ static int lti_dev_wc(pgps_ctx* ctx, size_t m, int d, const double* model, const
     a.sms = sms; a.sPs = sPs;
     TRY(launch_scan_wc<double>(ctx, a, d, MODE_PKFS));
     const int block = 256;
+    if (lin) {      // (the rows of C follow H in the model block: lti_model_in; a thread's step is J d^2 products: small blocks)
+        hipLaunchKernelGGL(k_project_rows_lin, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, (long)m, d, lin->J, qslot,
+                           a.H + d, (const double*)sms, (const double*)sPs, mean, lin->cov);
+        HIPCHK(ctx, hipGetLastError());
+        return PGPS_OK;
+    }
     hipLaunchKernelGGL(k_project_rows, dim3((unsigned)((m + block - 1) / block)), dim3(block), 0, ctx->stream, (long)m, d,
                        qslot, a.H, (const double*)sms, (const double*)sPs, mean, var);
     HIPCHK(ctx, hipGetLastError());
@@ -199,15 +261,18 @@ static int lti_dev_wc(pgps_ctx* ctx, size_t m, int d, const double* model, const
 
 // the small model [F | Pinf | H] from host memory, in ONE copy (three pageable copies were 15 us of a short series' call;
 // the source is staged by the runtime before the call returns, so it may change afterwards)
-int pgps::lti_model_in(pgps_ctx* ctx, int d, const double* F, const double* Pinf, const double* H, double** model) {
-    const size_t dd = (size_t)d * d;
-    TRY(ensure(ctx, ctx->lti[0], (2 * dd + d) * sizeof(double)));
+int pgps::lti_model_in(pgps_ctx* ctx, int d, const double* F, const double* Pinf, const double* H, double** model,
+                       const double* C, int J) {
+    const size_t dd = (size_t)d * d, nc = C ? (size_t)J * d : 0;
+    if (C && (J < 1 || J > PGPS_MAX_FUNCTIONALS)) return PGPS_E_INVALID;
+    TRY(ensure(ctx, ctx->lti[0], (2 * dd + d + nc) * sizeof(double)));
     *model = (double*)ctx->lti[0].p;
-    double host[2 * PGPS_MAX_DIM * PGPS_MAX_DIM + PGPS_MAX_DIM];
+    double host[2 * PGPS_MAX_DIM * PGPS_MAX_DIM + PGPS_MAX_DIM + PGPS_MAX_FUNCTIONALS * PGPS_MAX_DIM];
     std::memcpy(host, F, dd * sizeof(double));
     std::memcpy(host + dd, Pinf, dd * sizeof(double));
     std::memcpy(host + 2 * dd, H, (size_t)d * sizeof(double));
-    HIPCHK(ctx, hipMemcpyAsync(*model, host, (2 * dd + d) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (C) std::memcpy(host + 2 * dd + d, C, nc * sizeof(double));
+    HIPCHK(ctx, hipMemcpyAsync(*model, host, (2 * dd + d + nc) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     return PGPS_OK;
 }
 
@@ -215,13 +280,14 @@ int pgps::lti_model_in(pgps_ctx* ctx, int d, const double* F, const double* Pinf
 // everything on the device except the model
 int pgps::lti_core(pgps_ctx* ctx, size_t m, int d, const double* F, const double* Pinf, const double* H, double R,
                     const double* ts_m, const double* ys_m, double t0, const int* qslot, double* mean, double* var,
-                    double* ll) {
+                    double* ll, const LtiLin* lin) {
     const size_t dd = (size_t)d * d;
     double* model;
-    TRY(lti_model_in(ctx, d, F, Pinf, H, &model));
+    if (lin && !qslot) return PGPS_E_INVALID;
+    TRY(lti_model_in(ctx, d, F, Pinf, H, &model, lin ? lin->C : nullptr, lin ? lin->J : 0));
     double *Fs, *Qs = nullptr, *dll;
     TRY(stage_in<double>(ctx, ctx->st[11], nullptr, 2, &dll));
-    if (d > rc::kDimMax) return lti_dev_wc(ctx, m, d, model, F, Pinf, R, ts_m, ys_m, t0, qslot, mean, var, ll ? ll : dll);
+    if (d > rc::kDimMax) return lti_dev_wc(ctx, m, d, model, F, Pinf, R, ts_m, ys_m, t0, qslot, mean, var, ll ? ll : dll, lin);
     TRY(stage_in<double>(ctx, ctx->lti[4], nullptr, m * dd, &Fs));
     // the process noise stays implicit in both calls (Q_k = Pinf - F_k Pinf F_k^T inside the predict step): Qs is
     // never formed
@@ -234,6 +300,7 @@ int pgps::lti_core(pgps_ctx* ctx, size_t m, int d, const double* F, const double
     // scratch for the smoothing elements (E, g) where pkfs would have sPs, sms
     TRY(stage_in<double>(ctx, ctx->lti[6], nullptr, m * dd, &a.sPs));
     TRY(stage_in<double>(ctx, ctx->lti[7], nullptr, m * d, &a.sms));
+    if (lin) return launch_scan_rc_proj(ctx, a, d, MODE_PKFS, qslot, mean, nullptr, lin->J, model + 2 * dd + d, lin->cov);
     return launch_scan_rc_proj(ctx, a, d, MODE_PKFS, qslot, mean, var);
 }
 
@@ -262,12 +329,15 @@ int pgps::lti_filter_front(pgps_ctx* ctx, size_t m, int d, const double* F, cons
 
 static int lti_dev(pgps_ctx* ctx, long N, long K, int d, const double* F, const double* Pinf, const double* H, double R,
                    const double* ts, const double* ys, double t0, const double* tq, double* mean, double* var,
-                   double* ll) {
+                   double* ll, const LtiLin* lin = nullptr) {
     if (!ctx || N < 1 || K < 0 || !F || !Pinf || !H || !ts || !ys) return PGPS_E_INVALID;
-    if (K > 0 && (!tq || !mean || !var)) return PGPS_E_INVALID;
+    if (K > 0 && (!tq || !mean || (!var && !lin))) return PGPS_E_INVALID;
     if (K == 0 && !ll) return PGPS_E_INVALID;
+    if (lin && (K < 1 || !lin->C || !lin->cov || lin->J < 1 || lin->J > PGPS_MAX_FUNCTIONALS)) return PGPS_E_INVALID;
     if (d < rc::kDimMin || d > PGPS_MAX_DIM) return PGPS_E_UNSUPPORTED_DIM;
     if (N + K > 0x7fffffffL) return PGPS_E_INVALID;
+    // (the functionals flavour of the row-cooperative smoother addresses mean and cov with 32-bit byte offsets)
+    if (lin && d <= rc::kDimMax && (size_t)K * lin->J * lin->J * sizeof(double) > 0x7fff0000u) return PGPS_E_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t m = (size_t)(N + K);
     const double *ts_m = ts, *ys_m = ys;
@@ -277,27 +347,38 @@ static int lti_dev(pgps_ctx* ctx, long N, long K, int d, const double* F, const 
         TRY(merged_front<double>(ctx, ctx->lti + 1, N, K, ts, ys, tq, &mg));
         ts_m = mg.ts; ys_m = mg.ys; qslot = mg.qslot;
     }
-    return lti_core(ctx, m, d, F, Pinf, H, R, ts_m, ys_m, t0, qslot, mean, var, ll);
+    return lti_core(ctx, m, d, F, Pinf, H, R, ts_m, ys_m, t0, qslot, mean, var, ll, lin);
 }
 
+// host arrays in and out, staged once for both flavours (lin: mean (K, J) and lin->cov (K, J, J) on the HOST in place of var)
 static int lti_host(pgps_ctx* ctx, long N, long K, int d, const double* F, const double* Pinf, const double* H, double R,
                     const double* ts, const double* ys, double t0, const double* tq, double* mean, double* var,
-                    double* ll) {
+                    double* ll, const LtiLin* lin = nullptr) {
     if (!ctx || N < 1 || K < 0 || !ts || !ys) return PGPS_E_INVALID;
+    if (lin && (K < 1 || !lin->C || !lin->cov || lin->J < 1 || lin->J > PGPS_MAX_FUNCTIONALS)) return PGPS_E_INVALID;
+    if (lin) var = lin->cov;
     if (K > 0 && (!tq || !mean || !var)) return PGPS_E_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t J = lin ? (size_t)lin->J : 1, nm = (size_t)K * J, nv = lin ? nm * J : (size_t)K;
+    // the device call of either flavour: var is the block's place when there are functionals
+    auto run = [&](double* dts, double* dys, double* dtq, double* dmean, double* dvar, double* dll) {
+        if (!lin) return lti_dev(ctx, N, K, d, F, Pinf, H, R, dts, dys, t0, dtq, dmean, dvar, dll);
+        const LtiLin dl{lin->C, lin->J, dvar};
+        return lti_dev(ctx, N, K, d, F, Pinf, H, R, dts, dys, t0, dtq, dmean, nullptr, dll, &dl);
+    };
     {
-        SmallStage st(ctx, 2 * SmallStage::up((size_t)N * 8) + SmallStage::up((size_t)K * 8), 2 * SmallStage::up((size_t)K * 8) + 16);
+        SmallStage st(ctx, 2 * SmallStage::up((size_t)N * 8) + SmallStage::up((size_t)K * 8),
+                      SmallStage::up(nm * 8) + SmallStage::up(nv * 8) + 16);
         if (st.ok) {
             double llh = 0.0;
             double* dts_ = st.in(ts, (size_t)N);
             double* dys_ = st.in(ys, (size_t)N);
             double* dtq_ = K > 0 ? st.in(tq, (size_t)K) : nullptr;
             double* dll_ = st.out(&llh, 1);
-            double* dmean_ = K > 0 ? st.out(mean, (size_t)K) : nullptr;
-            double* dvar_ = K > 0 ? st.out(var, (size_t)K) : nullptr;
+            double* dmean_ = K > 0 ? st.out(mean, nm) : nullptr;
+            double* dvar_ = K > 0 ? st.out(var, nv) : nullptr;
             TRY(st.send());
-            TRY(lti_dev(ctx, N, K, d, F, Pinf, H, R, dts_, dys_, t0, dtq_, dmean_, dvar_, dll_));
+            TRY(run(dts_, dys_, dtq_, dmean_, dvar_, dll_));
             TRY(st.finish());
             if (ll) *ll = llh;
             return std::isfinite(llh) ? PGPS_OK : PGPS_E_NUMERIC;
@@ -308,14 +389,14 @@ static int lti_host(pgps_ctx* ctx, long N, long K, int d, const double* F, const
     TRY(stage_in(ctx, ctx->st[4], ys, (size_t)N, &dys));
     if (K > 0) {
         TRY(stage_in(ctx, ctx->st[3], tq, (size_t)K, &dtq));
-        TRY(stage_in<double>(ctx, ctx->st[7], nullptr, (size_t)K, &dmean));
-        TRY(stage_in<double>(ctx, ctx->st[8], nullptr, (size_t)K, &dvar));
+        TRY(stage_in<double>(ctx, ctx->st[7], nullptr, nm, &dmean));
+        TRY(stage_in<double>(ctx, ctx->st[8], nullptr, nv, &dvar));
     }
     TRY(stage_in<double>(ctx, ctx->st[9], nullptr, 2, &dll));
-    TRY(lti_dev(ctx, N, K, d, F, Pinf, H, R, dts, dys, t0, dtq, dmean, dvar, dll));
+    TRY(run(dts, dys, dtq, dmean, dvar, dll));
     if (K > 0) {
-        TRY(stage_out(ctx, mean, dmean, (size_t)K));
-        TRY(stage_out(ctx, var, dvar, (size_t)K));
+        TRY(stage_out(ctx, mean, dmean, nm));
+        TRY(stage_out(ctx, var, dvar, nv));
     }
     double llh = 0.0;
     TRY(stage_out(ctx, &llh, dll, 1));
@@ -448,6 +529,20 @@ extern "C" int pgps_lti_predict_dev_f64(pgps_ctx* c, long N, long K, int d, cons
                                         const double* tq, double* mean, double* var, double* ll) {
     if (K < 1) return PGPS_E_INVALID;
     return lti_dev(c, N, K, d, F, Pinf, H, R, ts, ys, t0, tq, mean, var, ll);
+}
+extern "C" int pgps_lti_predict_lin_f64(pgps_ctx* c, long N, long K, int d, int J, const double* F, const double* Pinf,
+                                        const double* H, const double* C, double R, const double* ts, const double* ys,
+                                        double t0, const double* tq, double* mean, double* cov, double* ll) {
+    if (K < 1) return PGPS_E_INVALID;
+    const LtiLin lin{C, J, cov};
+    return lti_host(c, N, K, d, F, Pinf, H, R, ts, ys, t0, tq, mean, nullptr, ll, &lin);
+}
+extern "C" int pgps_lti_predict_lin_dev_f64(pgps_ctx* c, long N, long K, int d, int J, const double* F, const double* Pinf,
+                                            const double* H, const double* C, double R, const double* ts, const double* ys,
+                                            double t0, const double* tq, double* mean, double* cov, double* ll) {
+    if (K < 1) return PGPS_E_INVALID;
+    const LtiLin lin{C, J, cov};
+    return lti_dev(c, N, K, d, F, Pinf, H, R, ts, ys, t0, tq, mean, nullptr, ll, &lin);
 }
 // ---------------------------------------------------------------------------------------------
 // batched predict_f for ANY kernel's LTI model (fp64, 2 <= d <= 16): B models [F | Pinf | H | R] over one series and one

@@ -1222,8 +1222,15 @@ __global__ __launch_bounds__(64) void rc_selem1(const RcArgsT<Real> a) {
 // ====================================================================================================
 // PROJ (pgps_lti_predict_*): nothing is stored per step; step k writes  H sm_k  and  H sP_k H^T  to slot qslot[k]
 // when that is >= 0 (StateSpaceGP.predict_f keeps exactly those, pssgp/model.py:107-111)
-template <typename Real, int D, bool FAST, bool PROJ>
+// LIN (with PROJ; pgps_lti_predict_lin_*): J = a.nfun functionals C (J, D) of the state instead of H -- step k writes
+// C sm_k (J) and C sP_k C^T (J, J) to slot qslot[k].  A lane keeps c_j[lane] (J registers, not J D): sP is symmetric bit
+// for bit after symmetrise, so its register i is also ROW lane's entry i and  w_j = (sP c_j)_lane  is one mvr; the means and
+// the entries i <= j of the block are row sums of c_j[lane] sm and c_i[lane] w_j.  Entry (i, j) is gathered into lane j of
+// row register i and into lane i of row register j -- the mirror is a copy, the block symmetric bit for bit -- and a row of
+// the block leaves in ONE store (lanes < J), as the mean does: 1 + J stores per step.
+template <typename Real, int D, bool FAST, bool PROJ, bool LIN = false>
 __device__ __forceinline__ void smooth1_body(const RcArgsT<Real>& a, Real* patch, char* wslots, int lane, int row) {
+    static_assert(!LIN || PROJ, "the functionals flavour is a flavour of the projecting smoother");
     constexpr int dd = D * D;
     const long kw = (long)blockIdx.x * 4 * a.Lw;
     const long c = (long)blockIdx.x * 4 + row;
@@ -1256,9 +1263,16 @@ __device__ __forceinline__ void smooth1_body(const RcArgsT<Real>& a, Real* patch
     zero<D>(Ec); zero<D>(Er); zero<D>(L);
     Real h[D];
     int q = -1;
-    if (PROJ) {
+    if (PROJ && !LIN) {
 #pragma unroll
         for (int i = 0; i < D; ++i) h[i] = a.H[i];
+    }
+    constexpr int JM = LIN ? PGPS_MAX_FUNCTIONALS : 1;
+    const int nfun = LIN ? a.nfun : 0;
+    Real cl[JM];
+    if constexpr (LIN) {
+#pragma unroll
+        for (int j = 0; j < JM; ++j) cl[j] = (j < nfun && lv) ? a.C[j * D + lane] : Real(0.0);
     }
     // stored element of this row's step; steps outside the chunk run as the identity element (I, 0, 0)
     auto load = [&](int s) {                    // the general body's per-register loads
@@ -1317,7 +1331,34 @@ __device__ __forceinline__ void smooth1_body(const RcArgsT<Real>& a, Real* patch
         }
         symmetrise<D, true>(nP, patch, lane);
         copy<D>(sP, nP);
-        if (PROJ) {
+        if constexpr (LIN) {
+            // (uniform branches on nfun; the offsets of a row's step are out of range unless it is a query; the entry points refuse 8 K J^2 > 0x7fff0000)
+            const bool on = qk >= 0 && lane < nfun;
+            Real mrow = Real(0.0), crow[JM];
+#pragma unroll
+            for (int j = 0; j < JM; ++j) crow[j] = Real(0.0);
+#pragma unroll
+            for (int j = 0; j < JM; ++j) {
+                if (j < nfun) {
+                    const Real mj = rowsum<D>(cl[j] * sm, Real(0.0));           // c_j sm          (every lane of the row)
+                    mrow = lane == j ? mj : mrow;
+                    const Real w = mvr<D>(sP, cl[j], Real(0.0));                // (sP c_j)_lane
+#pragma unroll
+                    for (int i = 0; i <= j; ++i) {
+                        const Real cij = rowsum<D>(cl[i] * w, Real(0.0));       // c_i sP c_j^T
+                        crow[i] = lane == j ? cij : crow[i];
+                        crow[j] = lane == i ? cij : crow[j];
+                    }
+                }
+            }
+            const unsigned J = (unsigned)nfun, qb = (unsigned)qk * J;
+            buf_st(make_rsrc(a.pmean, 0x7fff0000u), on ? (qb + (unsigned)lane) * (unsigned)sizeof(Real) : kOob, mrow);
+            const __amdgpu_buffer_rsrc_t rcov = make_rsrc(a.pcov, 0x7fff0000u);
+#pragma unroll
+            for (int i = 0; i < JM; ++i) {
+                if (i < nfun) buf_st(rcov, on ? ((qb + (unsigned)i) * J + (unsigned)lane) * (unsigned)sizeof(Real) : kOob, crow[i]);
+            }
+        } else if (PROJ) {
             const Real mean = mvr<D>(h, sm, Real(0.0));                     // H sm            (every lane of the row)
             const Real var = mvr<D>(h, dot_h<D>(sP, h), Real(0.0));         // H sP H^T
             // branch-free: a descriptor over the K outputs, offset out of range unless this step is a query (lane 0 writes)
@@ -1333,7 +1374,7 @@ __device__ __forceinline__ void smooth1_body(const RcArgsT<Real>& a, Real* patch
     }
 }
 
-template <typename Real, int D, bool PROJ>
+template <typename Real, int D, bool PROJ, bool LIN = false>
 __global__ __launch_bounds__(64) void rc_smooth1(const RcArgsT<Real> a0) {
     const RcArgsT<Real> a = model_view(a0);
     __shared__ Real tl[4 * kPatch];
@@ -1344,11 +1385,11 @@ __global__ __launch_bounds__(64) void rc_smooth1(const RcArgsT<Real> a0) {
     // FAST: the four chains are complete (the smoother reads nothing beyond its chains: the first and the last workgroup of
     // a series qualify like any other -- until round 3 they took the general body, whose wave a one-round grid waits for)
     const bool full = ((long)blockIdx.x + 1) * 4 * a.Lw <= a.N;
-    if (PGPS_RC_EDGE_FAST != 0 ? full : (blockIdx.x >= 1 && blockIdx.x < a.wfast)) smooth1_body<Real, D, true, PROJ>(a, patch, wslots, lane, row);
+    if (PGPS_RC_EDGE_FAST != 0 ? full : (blockIdx.x >= 1 && blockIdx.x < a.wfast)) smooth1_body<Real, D, true, PROJ, LIN>(a, patch, wslots, lane, row);
 #ifdef PGPS_RC_SKIP_EDGE               // (timing experiment: what the kernel costs without its edge waves; results are wrong)
     else return;
 #else
-    else smooth1_body<Real, D, false, PROJ>(a, patch, wslots, lane, row);
+    else smooth1_body<Real, D, false, PROJ, LIN>(a, patch, wslots, lane, row);
 #endif
 }
 
@@ -1867,7 +1908,7 @@ __global__ __launch_bounds__(64) void rc_discretise(long N, int per, const doubl
 
 // ---- host side: the level-1 launches of one instantiation ---------------------------------------------
 // phase 0: reduce, 1: apply + smoothing elements, 2: apply only, 3: smoother, 4: smoother writing projections,
-// 5: smoothing elements from given filtered moments (stand-alone pks)
+// 5: smoothing elements from given filtered moments (stand-alone pks), 6: smoother writing functionals (a.nfun, a.C, a.pcov)
 template <typename Real, int D>
 int launch_rc_level1(pgps_ctx* ctx, const RcArgsT<Real>& a, int phase) {
     const dim3 blk(64), g1((unsigned)((a.nchunk + 3) / 4), (unsigned)(a.batch > 1 ? a.batch : 1));
@@ -1890,6 +1931,10 @@ int launch_rc_level1(pgps_ctx* ctx, const RcArgsT<Real>& a, int phase) {
             break;
         case 3: timed_launch(ctx, PGPS_K_SMOOTHER_APPLY, rc_smooth1<Real, D, false>, g1, blk, 0u, a); break;
         case 5: timed_launch(ctx, PGPS_K_SMOOTHER_REDUCE, rc_selem1<Real, D>, g1, blk, 0u, a); break;
+        case 6:                                 // smoother writing the functionals C sm, C sP C^T (fp64 only)
+            if constexpr (std::is_same<Real, double>::value) timed_launch(ctx, PGPS_K_SMOOTHER_APPLY, rc_smooth1<Real, D, true, true>, g1, blk, 0u, a);
+            else return PGPS_E_INVALID;
+            break;
         default: timed_launch(ctx, PGPS_K_SMOOTHER_APPLY, rc_smooth1<Real, D, true>, g1, blk, 0u, a); break;
     }
     HIPCHK(ctx, hipGetLastError());

@@ -2406,7 +2406,7 @@ static int scan_rc(pgps_ctx* ctx, int d, RcArgsT<Real> a, Mode mode, Real* aggA,
         src = saggA;
         if ((rcode = ks_scan(ctx, d, 1, a.nchunk, saggA, saggB, &src, nb, a.bs_sagg, geom_batch))) return rcode;
         a.suf = src;
-        if ((rcode = level1(ctx, d, a, a.qslot ? 4 : 3))) return rcode;
+        if ((rcode = level1(ctx, d, a, a.qslot ? (a.nfun > 0 ? 6 : 4) : 3))) return rcode;
     } else {
         if ((rcode = level1(ctx, d, a, 2))) return rcode;
     }
@@ -2444,7 +2444,8 @@ static inline long rc_batch_chain_steps(long N, int B) {
 
 template <typename Real>
 static int scan_rc_entry(pgps_ctx* ctx, ScanArgs<Real> sa, int d, Mode mode, int store_f, const int* qslot, Real* pmean,
-                         Real* pvar, int batch = 1, long bs_model = 0, int geom_batch = 0, long bs_out = 0);
+                         Real* pvar, int batch = 1, long bs_model = 0, int geom_batch = 0, long bs_out = 0, int nfun = 0,
+                         const Real* C = nullptr, Real* pcov = nullptr);
 
 // 2 <= d <= 16, pkf / pks / pkfs on one device and the three segment phases
 template <typename Real>
@@ -2453,10 +2454,12 @@ int launch_scan_rc(pgps_ctx* ctx, ScanArgs<Real> sa, int d, Mode mode) {
 }
 template int launch_scan_rc<double>(pgps_ctx*, ScanArgs<double>, int, Mode);
 template int launch_scan_rc<float>(pgps_ctx*, ScanArgs<float>, int, Mode);
-int launch_scan_rc_proj(pgps_ctx* ctx, ScanArgs<double> sa, int d, Mode mode, const int* qslot, double* pmean, double* pvar) {
+int launch_scan_rc_proj(pgps_ctx* ctx, ScanArgs<double> sa, int d, Mode mode, const int* qslot, double* pmean, double* pvar,
+                        int nfun, const double* C, double* pcov) {
     RoctxRange range_("parallel_filter");
-    if (mode == MODE_PKFS && (!qslot || !pmean || !pvar)) return PGPS_E_INVALID;
-    return scan_rc_entry<double>(ctx, sa, d, mode, 0, mode == MODE_PKFS ? qslot : nullptr, pmean, pvar);
+    if (nfun != 0 && (mode != MODE_PKFS || nfun < 0 || nfun > PGPS_MAX_FUNCTIONALS || !C || !pcov)) return PGPS_E_INVALID;
+    if (mode == MODE_PKFS && (!qslot || !pmean || (!pvar && nfun == 0))) return PGPS_E_INVALID;
+    return scan_rc_entry<double>(ctx, sa, d, mode, 0, mode == MODE_PKFS ? qslot : nullptr, pmean, pvar, 1, 0, 0, 0, nfun, C, pcov);
 }
 
 int launch_ll_batch_rc(pgps_ctx* ctx, long N, int d, int batch, const double* table, long bs_model, const double* Fs,
@@ -2491,7 +2494,7 @@ int launch_predict_batch_rc(pgps_ctx* ctx, long N, long K, int d, int batch, int
 
 template <typename Real>
 static int scan_rc_entry(pgps_ctx* ctx, ScanArgs<Real> sa, int d, Mode mode, int store_f, const int* qslot, Real* pmean,
-                         Real* pvar, int batch, long bs_model, int geom_batch, long bs_out) {
+                         Real* pvar, int batch, long bs_model, int geom_batch, long bs_out, int nfun, const Real* C, Real* pcov) {
     const bool seg = mode == MODE_SEG_REDUCE || mode == MODE_SEG_FILTER || mode == MODE_SEG_SMOOTHER;
     if (d < rc::kDimMin || d > rc::kDimMax) return PGPS_E_UNSUPPORTED_DIM;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -2532,6 +2535,8 @@ static int scan_rc_entry(pgps_ctx* ctx, ScanArgs<Real> sa, int d, Mode mode, int
     a.P0 = sa.P0; a.H = sa.H; a.R = sa.R; a.Fs = sa.Fs; a.Qs = sa.Qs; a.ys = sa.ys;
     a.fms = sa.fms; a.fPs = sa.fPs; a.sms = sa.sms; a.sPs = sa.sPs;
     a.store_f = store_f; a.qslot = qslot; a.pmean = pmean; a.pvar = pvar;
+    // (the functionals flavour changes what the projecting smoother writes and nothing before it: same chains, same scans)
+    a.nfun = qslot ? nfun : 0; a.C = C; a.pcov = pcov;
     // whole-series filter + smoother with every moment stored: the chains' smoothing totals in innovation form (pgps_rc.hip.h,
     // apply1_body DFORM); -DPGPS_RC_DFORM=0 keeps the reference's form everywhere (A/B)
 #ifndef PGPS_RC_DFORM

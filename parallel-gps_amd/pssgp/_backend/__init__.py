@@ -11,8 +11,8 @@ from .library import (COMM_ID_BYTES, E_NUMERIC, E_UNSUPPORTED_DIM, PGPS_K_NAMES,
 from .context import Context, _contexts, get_context
 from .arrays import _prep, _ptr, _scalar_out, _series_inputs, _suffix
 from .lgssm import _cov_inputs, _dtype_of, _sample_inputs, _unpack_lgssm, discretise, pkf, pkfs, pks, pks_cov, pks_sample
-from .lti import (LTI_BATCH_DIM_MAX, LTI_DIM_MAX, LTI_DIM_MIN, LtiGradStream, LtiLlStream, _lti_model, contract_grad_stats, lti_ll,
-                  lti_ll_grad, lti_predict, lti_predict_cov, lti_predict_stream, lti_sample, split_grad_stats)
+from .lti import (LTI_BATCH_DIM_MAX, LTI_DIM_MAX, LTI_DIM_MIN, LTI_FUNCTIONALS_MAX, LtiGradStream, LtiLlStream, _lti_model, contract_grad_stats, lti_ll,
+                  lti_ll_grad, lti_predict, lti_predict_cov, lti_predict_lin, lti_predict_stream, lti_sample, split_grad_stats)
 from .fused import (GRAD_BLOCKS_DIM_MAX, GRAD_BLOCKS_MAX, GRAM_COLUMNS_MAX, gp, gp_gram_multi, gp_ll_grad, gp_ll_grad_adj_het,
                     gp_ll_grad_blocks, gp_ll_grad_multi, gp_ll_het, gp_ll_multi, gp_loo, gp_predict, gp_predict_het,
                     gp_predict_multi, gp_whiten_multi, nilpotent_blocks, nilpotent_form, normal_log_density, pack_grad_model)

@@ -87,6 +87,7 @@ _SIGNATURES = (
     # general LTI models (F, Pinf, H)
     ("pgps_lti_ll{dev}_f64 pgps_lti_ll_grad{dev}_f64", "PLIPPPDPPDP"),
     ("pgps_lti_predict{dev}_f64 pgps_lti_predict_cov{dev}_f64", "PLLIPPPDPPDPPPP"),
+    ("pgps_lti_predict_lin{dev}_f64", "PLLIIPPPPDPPDPPPP"),
     ("pgps_lti_sample{dev}_f64", "PLLIPPPDPPDPILUPP"),
     # B models at once
     ("pgps_gp_ll_batch{dev}_{suf} pgps_gp_ll_grad_adj_batch{dev}_f64", "PILIPPDPP"),

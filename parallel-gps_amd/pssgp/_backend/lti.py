@@ -9,6 +9,7 @@ from .library import _require, c_double, c_int, c_long, c_void_p
 # state dimensions of the general-LTI device path: row-cooperative kernels up to 16 (batched evaluation only there),
 # wave-cooperative kernels from 17 to 32
 LTI_DIM_MIN, LTI_DIM_MAX, LTI_BATCH_DIM_MAX = 2, 32, 16
+LTI_FUNCTIONALS_MAX = 8         # PGPS_MAX_FUNCTIONALS: rows of C in one pgps_lti_predict_lin_* call
 
 
 def _lti_model(F, Pinf, H):
@@ -73,6 +74,24 @@ def lti_predict(F, Pinf, H, R, ts, ys, tq, t0=0.0, device=0):
     get_context(device).call("pgps_lti_predict_f64", N, K, d, _ptr(F), _ptr(Pinf), _ptr(H), float(R), _ptr(ts_a), _ptr(ys_a),
                              float(t0), _ptr(tq_a), _ptr(mean), _ptr(var), llp)
     return mean, var, ll.value
+
+
+def lti_predict_lin(F, Pinf, H, C, R, ts, ys, tq, t0=0.0, device=0):
+    """The posterior of J linear functionals C x of the state at the query times (pgps_lti_predict_lin_f64): the chain of
+    lti_predict -- merge, discretisation, filter + smoother over the N + K steps, H the observation row -- with
+    mean (K, J) = C sm and cov (K, J, J) = C sP C^T of every query step, each block symmetric bit for bit.  C (J, d),
+    1 <= J <= LTI_FUNCTIONALS_MAX.  Returns (mean, cov, ll of the training series)."""
+    F, Pinf, H, d = _lti_model(F, Pinf, H)
+    C = _prep(C, np.float64, (-1, d))
+    J = C.shape[0]
+    ts_a, ys_a, tq_a, N = _series_inputs(ts, ys, tq)
+    K = tq_a.shape[0]
+    mean, cov = np.empty((K, J), np.float64), np.empty((K, J, J), np.float64)
+    ll, llp = _scalar_out()
+    ctx = _require(get_context(device), "pgps_lti_predict_lin_f64", "pgps_lti_predict_lin_*")
+    ctx.call("pgps_lti_predict_lin_f64", N, K, d, J, _ptr(F), _ptr(Pinf), _ptr(H), _ptr(C), float(R), _ptr(ts_a), _ptr(ys_a),
+             float(t0), _ptr(tq_a), _ptr(mean), _ptr(cov), llp)
+    return mean, cov, ll.value
 
 
 def _small_lti_model(F, Pinf, H):

@@ -106,6 +106,21 @@ def _tree_ids(k):
     return (id(k), tuple(_tree_ids(x) for x in subs) if subs else (), id(base) if base is not None else 0)
 
 
+def _part_name(kernel, index):
+    name = getattr(kernel, "name", None)
+    return str(name) if name else f"{type(kernel).__name__}{index}"
+
+
+def _driven_directions(L, Q):
+    """Columns spanning the directions in which the noise of dx = F x dt + L dbeta, E dbeta dbeta^T = Q dt, reaches the
+    state: the columns of L with a positive spectral density where Q is diagonal (every leaf kernel, sums of them), the
+    columns of L Q L^T / max |Q| otherwise (products: L = I and a singular matrix Q; c G = 0 iff c G c^T = 0 for G >= 0)."""
+    diag = np.diag(Q)
+    if not np.any(Q - np.diag(diag)):
+        return L[:, diag > 0.0]
+    return L @ (Q / float(np.max(np.abs(Q)))) @ L.T
+
+
 class SDEKernelMixin:
     """`get_sde()` -> continuous model; `get_ssm(ts, R, t0)` -> LGSSM (base.py:50-103)."""
 
@@ -145,6 +160,34 @@ class SDEKernelMixin:
 
     def get_spec(self, T):
         raise NotImplementedError
+
+    # -- linear functionals of the state, in the coordinates of get_sde() -----------
+    def component_functionals(self):
+        """(names, C (J, d)): the additive parts of f = H x as rows over the state of get_sde().  A sum kernel has one row per
+        (flattened) summand -- H with every column outside that part's block set to 0, so the rows add up to H exactly; any
+        other kernel is one part, C = H.  names: the part's `name` where it has one, else its class name and index."""
+        H = np.asarray(self.get_sde().H, np.float64).reshape(1, -1)
+        return [_part_name(self, 0)], H.copy()
+
+    def derivative_functional(self, order=1):
+        """c (d,) = H F^order with f^(order)(t) = c x(t), for the model of get_sde().  f = H x of dx = F x dt + L dbeta is
+        `order` times mean-square differentiable iff H F^j L = 0 for every j < order (the noise must not reach f^(j) directly);
+        ValueError otherwise.  The test is  max |H F^j L| <= 1e-12 max(1, |H F^j|_inf |L|_inf), L restricted to the directions
+        the noise drives (_driven_directions: Periodic has L = I and Q = 0, products L = I and a singular Q).  order = 0: H."""
+        order = int(order)
+        if order < 0:
+            raise ValueError(f"order must be >= 0, got {order}")
+        sde = self.get_sde()
+        F = np.asarray(sde.F, np.float64)
+        L = _driven_directions(np.asarray(sde.L, np.float64), np.atleast_2d(np.asarray(sde.Q, np.float64)))
+        c = np.asarray(sde.H, np.float64).reshape(-1).copy()
+        # (column by column: one part's large L -- an unbalanced RBF's is 1e6 -- must not hide another part's H L = 1)
+        Lmax = np.max(np.abs(L), axis=0) if L.size else np.zeros(0)
+        for j in range(order):
+            if np.any(np.abs(c @ L) > 1e-12 * np.maximum(1.0, float(np.max(np.abs(c))) * Lmax)):
+                raise ValueError(f"{type(self).__name__} is not {order} times mean-square differentiable: H F^{j} L != 0")
+            c = c @ F
+        return c
 
     def __add__(self, other):
         return SDESum([self, other])
@@ -210,6 +253,17 @@ class SDESum(_Combination):
         if Pinf is None:
             Pinf = solve_lyap_vec(Fb, Lb, Qb)
         return ContinuousDiscreteModel(Pinf, Fb, Lb, Hb, Qb)
+
+    def component_functionals(self):
+        # block j's columns are the running sum of the parts' state dimensions; balancing is a diagonal scaling and keeps them
+        H = np.asarray(self.get_sde().H, np.float64).reshape(-1)
+        dims = [np.asarray(k.get_sde().F).shape[0] for k in self.kernels]
+        C = np.zeros((len(dims), H.shape[0]), np.float64)
+        start = 0
+        for j, dj in enumerate(dims):
+            C[j, start:start + dj] = H[start:start + dj]
+            start += dj
+        return [_part_name(k, j) for j, k in enumerate(self.kernels)], C
 
 
 class SDEProduct(_Combination):

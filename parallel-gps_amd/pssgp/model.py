@@ -9,7 +9,8 @@ the scan kernels) instead of TensorFlow autodiff.
 
 This module holds the model's data, the residency of its series on the device, the public evaluations and the routing
 between their paths; the kernel's device forms are forms.py's, the gradient methods gradients.py's, the batched
-evaluations batches.py's, the predictive checks checks.py's, the mean function's evaluations trend.py's (mixins of the one class).
+evaluations batches.py's, the predictive checks checks.py's, the mean function's evaluations trend.py's, the functionals of the
+state (additive components, derivatives) functionals.py's (mixins of the one class).
 """
 import numpy as np
 
@@ -18,6 +19,7 @@ from ._evaluation import _mean_function_route, _multi_output, _public_evaluation
 from .batches import ModelBatches
 from .checks import ModelChecks
 from .forms import ModelForms
+from .functionals import ModelFunctionals
 from .gradients import ModelGradients, mask_wrt
 from .kalman.parallel import pkf, pkfs
 from .kalman import sequential
@@ -98,7 +100,7 @@ def _as_columns(data):
     return (ts[:, None] if ts.ndim == 1 else ts), (ys[:, None] if ys.ndim == 1 else ys)
 
 
-class StateSpaceGP(ModelForms, ModelGradients, ModelBatches, ModelChecks, ModelTrend):
+class StateSpaceGP(ModelForms, ModelGradients, ModelBatches, ModelChecks, ModelTrend, ModelFunctionals):
     """GP regression on one input (time) axis.  Y (N, 1) is the reference's model.
 
     THE FUSED ROUTE.  The evaluations below that name it run the fused HIP kernels on host arrays when: parallel=True, a single
@@ -140,7 +142,13 @@ class StateSpaceGP(ModelForms, ModelGradients, ModelBatches, ModelChecks, ModelT
     Everything else -- parallel=False, float32, other kernels, times out of order, more columns -- is the host twin: the
     sequential filter's innovations column by column, any kernel.  Y with more than one column, observation_variances,
     log_likelihood_batch, log_likelihood_and_grad_batch and predict_f_batch (their thetas layout has no place for beta) raise
-    NotImplementedError; a design matrix without full column rank on the observed rows raises ValueError."""
+    NotImplementedError; a design matrix without full column rank on the observed rows raises ValueError.
+
+    Functionals of the state (functionals.py): predict_components -- the posterior of every additive part of a sum kernel --,
+    predict_f_derivative and predict_functionals (any C (J, d) over the state of kernel.get_sde()): mean (K, J) = C sm and
+    cov (K, J, J) = C sP C^T at the query times.  parallel=True, sorted training times, 2 <= d <= 32, J <= 8: one device call
+    (_backend.lti_predict_lin); everything else the host twin (_host_smoothed), any kernel.  Single-output models with one
+    noise variance and no mean function."""
 
     def __init__(self, data, kernel, noise_variance=1.0, parallel=False, max_parallel=10000, observation_variances=None,
                  mean_function=None):
@@ -474,11 +482,12 @@ class StateSpaceGP(ModelForms, ModelGradients, ModelBatches, ModelChecks, ModelT
             H = np.asarray(ssm.H)
         return _project(sms, sPs, all_flags, H)
 
-    def _host_smoothed(self, tq):
+    def _host_smoothed(self, tq, data=None):
         """Merge with the (sorted) queries tq, discretisation (_host_discretise), sequential filter + smoother at the model's
         current setting on the host alone, fp64.  (ssm, h, fPs, sms, sPs, ll, flags): the query rows are missing
-        observations and add nothing to the log-likelihood."""
-        ts, ys = self.data
+        observations and add nothing to the log-likelihood.  `data`: (ts, ys) to run on in place of the model's (a sorted
+        copy of them)."""
+        ts, ys = self.data if data is None else data
         all_ts, all_ys, all_flags = _merge_queries(np.asarray(ts, np.float64).reshape(-1), np.asarray(ys, np.float64),
                                                    np.asarray(tq, np.float64))
         sde = self.kernel.get_sde()
