@@ -605,6 +605,44 @@ int pgps_gp_ll_grad_adj_het_dev_f64(pgps_ctx*, long N, int d, double lam, const 
                                     const double* Pinf, const double* H, double R, const double* ts, double t0,
                                     const double* ys, const double* rs, double* out /* 1 + d d + 2 d + 1 */);
 
+/* ---- a panel: S independent series, each on its own clock and of its own length (fused path, fp64, d <= 3) ----
+ * Light curves of a survey, one record per patient or sensor, the folds of a cross-validation: series of 10^2 .. 10^3 points,
+ * where one evaluation is bound by launch latency.  A panel call gives every series ONE workgroup of ONE launch.
+ *   offs    (S + 1) HOST, strictly increasing from 0: series s is rows offs[s] .. offs[s + 1] of the concatenated ts, ys, rs
+ *           (each series sorted by time, NaN in ys = missing)
+ *   qoffs   (S + 1) HOST, non-decreasing from 0: its queries are rows qoffs[s] .. qoffs[s + 1] of tq (sorted per series), and of
+ *           mean / var; a series may have none (it still returns its ll); qoffs[S] >= 1
+ *   models  HOST, nmodels rows [lam | N1 (d d) | N2 (d d) | Pinf (d d) | H (d) | R] as pgps_gp_ll_batch_* takes them; nmodels = 1
+ *           (shared by all series) or S (row s for series s)
+ *   rs      per-observation noise variances as pgps_gp_ll_het_* take them (read at observed rows only, R + rs[k] > 0), or NULL:
+ *           scalar noise R
+ *   ll      (S); out (S, 1 + d d + 2 d + 1) rows [ll | Abar | Ubar | Hbar | Rbar] as pgps_gp_ll_grad_adj_dev_f64 lays them out.
+ * Row s is what the single-series call on series s computes (t0 = the series' first time; the predict call merges as
+ * pgps_gp_predict_* does, per series).  A series is limited to PGPS_PANEL_MAX_STEPS steps, counted MERGED (n + k) in predict.  Each
+ * series takes max(1, ceil(steps / 256)) steps per lane (pgps_set_chunk: the pinned value wherever it covers the series), so a
+ * row's bits depend on that series alone: not on the other series, on its place, on repetition, or on how the series are split
+ * into groups that fit pgps_set_batch_scratch (at most 65535 series per launch).
+ * Host forms take host arrays, scan rs once (PGPS_E_INVALID where the rule fails) and return PGPS_E_NUMERIC on a non-finite ll;
+ * _dev forms take device pointers for everything but offs / qoffs / models, synchronise the context's stream ONCE to copy their
+ * tables in and are asynchronous afterwards (the rule of rs is a PRECONDITION).  Errors: S < 1, a null pointer (rs, and ll of
+ * predict, excepted), an empty series, a series above PGPS_PANEL_MAX_STEPS, qoffs[S] < 1, nmodels not 1 or S, lam <= 0 or R < 0
+ * in a row, R <= 0 in a row when rs is NULL: PGPS_E_INVALID; d outside 1..3: PGPS_E_UNSUPPORTED_DIM. */
+#define PGPS_PANEL_MAX_STEPS 2048
+int pgps_gp_panel_ll_f64(pgps_ctx*, long S, const long* offs, int d, int nmodels, const double* models, const double* ts,
+                         const double* ys, const double* rs, double* ll);
+int pgps_gp_panel_ll_dev_f64(pgps_ctx*, long S, const long* offs, int d, int nmodels, const double* models, const double* ts,
+                             const double* ys, const double* rs, double* ll);
+int pgps_gp_panel_ll_grad_f64(pgps_ctx*, long S, const long* offs, int d, int nmodels, const double* models, const double* ts,
+                              const double* ys, const double* rs, double* out);
+int pgps_gp_panel_ll_grad_dev_f64(pgps_ctx*, long S, const long* offs, int d, int nmodels, const double* models,
+                                  const double* ts, const double* ys, const double* rs, double* out);
+int pgps_gp_panel_predict_f64(pgps_ctx*, long S, const long* offs, const long* qoffs, int d, int nmodels, const double* models,
+                              const double* ts, const double* ys, const double* rs, const double* tq, double* mean,
+                              double* var, double* ll);
+int pgps_gp_panel_predict_dev_f64(pgps_ctx*, long S, const long* offs, const long* qoffs, int d, int nmodels,
+                                  const double* models, const double* ts, const double* ys, const double* rs, const double* tq,
+                                  double* mean, double* var, double* ll);
+
 /* ---- predictive checks of a fitted model against its own data (fused path, fp64, d <= 3) --------------
  * Two laws of every y_k, from ONE filter and ONE smoother pass over the N training steps (no merge, no query rows):
  *   osa_mean, osa_var   y_k given the observations BEFORE it: N(H m_k^-, H P_k^- H^T + R), the pair the Kalman pass hands to its

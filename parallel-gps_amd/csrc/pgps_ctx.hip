@@ -95,6 +95,7 @@ extern "C" int pgps_destroy(pgps_ctx* ctx) {
     if (ctx->stamps.p) (void)hipFree(ctx->stamps.p);
     if (ctx->res_stamps.p) (void)hipFree(ctx->res_stamps.p);
     if (ctx->gadj.p) (void)hipFree(ctx->gadj.p);
+    if (ctx->panel.p) (void)hipFree(ctx->panel.p);
     if (ctx->pin_d.p) (void)hipFree(ctx->pin_d.p);
     if (ctx->pin_h) (void)hipHostFree(ctx->pin_h);
     if (ctx->out_h) (void)hipHostFree(ctx->out_h);

@@ -66,7 +66,8 @@ __device__ __forceinline__ void gp_prior(const GpModel<T>& m, T* h, T* P0 /*sym*
 // per-observation noise variances: a compile-time flavour of the bodies below, HET, off by default --
 // the scalar instantiations are what they were.  With HET a body takes `rs` (N given variances s_k), a lane loads rs[k + 1]
 // next to its prefetch of ts[k + 1], ys[k + 1], and the step's noise variance is R + s_k.  At a missing step the loaded value
-// never reaches the add (it may be NaN).  Instantiated in pgps_het_inst.hip only.
+// never reaches the add (it may be NaN).  Instantiated in pgps_het_inst.hip, pgps_site_inst.hip and (one workgroup per series)
+// pgps_panel_inst.hip.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 __device__ __forceinline__ T het_noise(T R, T r, T y) {

@@ -6,7 +6,8 @@
 // ts[k + 1], ys[k + 1] and hands R + s_k to filt_first / filt_extend / kf_step / adj_step in place of R (het_noise: at a missing
 // step the loaded value is replaced by 0 before the add, so it may be anything, NaN included).  The smoother never sees R: it is
 // k_gp_smooth itself.  Three-launch forms only: reduce / Kalman pass / smoother with projection, and reduce / adjoint forward /
-// adjoint backward (+ the finalize of the partials); no one-workgroup form, no resident launch, no streaming stores.
+// adjoint backward (+ the finalize of the partials); no one-workgroup form here (the panel has them: pgps_panel.hip.h), no resident
+// launch, no streaming stores.
 #include "pgps_gpadj.hip.h"
 #include "pgps_het.hip.h"
 #include "pgps_scratch.h"

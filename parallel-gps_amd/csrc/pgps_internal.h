@@ -62,6 +62,7 @@ struct pgps_ctx {
     DevBuf pin_d;                       // its device twin
     char* out_h = nullptr;              // pinned staging of the batched predict's (B, K) results on their way to pageable host arrays
     size_t out_cap = 0;
+    DevBuf panel;                       // ragged batch of series (pgps_panel_inst.hip): [model table | descriptor table]
     DevBuf gadj;                        // fused-path adjoint gradient (pgps_gpadj.hip.h): kept states of the forward pass, workgroup partials
     DevBuf wide[9];                     // fp64 copies of a promoted float32 call's arrays: P0, H, Fs, Qs, ys, fms, fPs, sms, sPs
     DevBuf smp;                         // backward sampler (pgps_sample.hip.h): lane suffixes and spine of every sample group
@@ -367,6 +368,62 @@ template <int D>
 int launch_gp_het(pgps_ctx* ctx, GpArgs<double> g, const double* rs);
 template <int D>
 int launch_gp_adj_het(pgps_ctx* ctx, GpArgs<double> g, const double* rs, double* out);
+
+// S independent series, each on its own clock and of its own length, in one launch per group (pgps_panel.hip.h,
+// pgps_panel_inst.hip; fp64, d <= 3).  One record per series, in device memory:
+struct PanelDesc {
+    long row0;              // first row in the concatenated ts / ys / rs
+    long q0;                // first query in tq / mean / var
+    long m0;                // first row of its merged slot in ts_m / ys_m / rs_m / qslot (a multiple of kPanelAlign)
+    long o_fm, o_fP;        // element offsets of its fms / fPs slices in its group's scratch (multiples of kPanelAlign)
+    long o_xs;              // ... of its kept states, ((d + sym) Lc, kBlock)
+    int n;                  // length
+    int k;                  // queries (0 in the likelihood and gradient calls)
+    int m;                  // merged length n + k
+    int Lc;                 // steps per lane, from m and the pinned chunk alone
+    int slot;               // its place in its group: the fixed-size records (lpre, lsuf, spine, sspine, llpart, gpart) of a
+                            // series lie at slot * record length
+    int model;              // its row of the model table
+};
+// Alignment of a panel's ragged slices, in ELEMENTS (doubles: 256 bytes; the int qslot: 128 bytes).
+//   merged slots   k_panel_merge stores four outputs per lane as 16-byte vectors (merge_sorted_body): it relies on outputs that
+//                  start 16-byte aligned.  Ragged series' slots would start anywhere: every slot is padded to kPanelAlign.
+//   fms / fPs      the staged stores of gp_apply_body and the staged loads of gp_smooth_body go through GpLds::stage in 16-byte
+//                  pieces from the slice's base: every series' slice starts on a multiple of kPanelAlign.
+constexpr int kPanelAlign = 32;
+// what one launch (one group of series: series blockIdx.y of the launch) sees
+struct PanelArgs {
+    const PanelDesc* desc;      // the group's records
+    const double* models;       // (nmodels, kGpModelStride) rows [lam | N1 | N2 | Pinf | H | R]
+    const double *ts, *ys, *rs; // concatenated training series (rs: null = scalar noise)
+    const double* tq;           // concatenated queries
+    double *ts_m, *ys_m, *rs_m; // merged slots of the group's series that have queries
+    int* qslot;                 // ... a query row's GLOBAL position in pmean / pvar, -1 at the training rows
+    double *pmean, *pvar;       // (all queries of the call,)
+    double* ll;                 // (the group's series,)
+    double* out;                // (the group's series, 1 + d^2 + 2 d + 1): gradient rows
+    double *spine, *lpre, *sspine, *lsuf, *llpart, *fms, *fPs, *xs, *gpart;     // the group's scratch
+    int* status;
+};
+// a call as the C ABI hands it over: offs / qoffs / models HOST, everything else device
+struct PanelCall {
+    long S;
+    const long* offs;           // (S + 1)
+    const long* qoffs;          // (S + 1), predict only
+    int nmodels;                // 1 or S
+    const double* models;       // (nmodels, kGpModelStride)
+    const double *ts, *ys, *rs, *tq;
+    double *mean, *var;         // predict
+    double* ll;                 // (S,)
+    double* out;                // gradient: (S, 1 + d^2 + 2 d + 1)
+};
+enum PanelWhat { PANEL_LL = 0, PANEL_GRAD = 1, PANEL_PREDICT = 2 };
+// lays the series out in groups that fit the context's batch budget, copies the two tables in (ONE stream synchronisation),
+// then merge (predict) and one launch per group.  The caller has checked the arguments
+template <int D>
+int launch_gp_panel(pgps_ctx* ctx, const PanelCall& c, PanelWhat what);
+// the segmented merge of one group (the d = 1 unit holds it): grid (tiles, series)
+int launch_panel_merge(pgps_ctx* ctx, const PanelArgs& p, unsigned tiles, unsigned series);
 
 // predictive checks of a fitted model against its own data on the fused path (pgps_loo_inst.hip; fp64, d <= 3):
 // what the OSA flavour of the Kalman pass and the LOO flavour of the smoother write

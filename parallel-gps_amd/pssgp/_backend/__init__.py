@@ -5,7 +5,7 @@ There is no CPU fallback: if the library is missing or no MI355X is visible the 
 This module only re-exports; `from pssgp import _backend` stays the one import.  Callers reach every entry point as
 `_backend.NAME(...)` at call time, so a name patched here is the one the model layer sees.  Where each concern lives:
 library (path, loading, the signature table, errors), context, arrays (input preparation shared by all calls), lgssm,
-fused, lti, series, batch, sites (Laplace inference)."""
+fused, lti, series, batch, sites (Laplace inference), panel (S series on their own clocks)."""
 from .library import (COMM_ID_BYTES, E_NUMERIC, E_UNSUPPORTED_DIM, PGPS_K_NAMES, PGPS_OK, PgpsError, _LIB_PATH, _require, check,
                       load_library, signatures)
 from .context import Context, _contexts, get_context
@@ -19,5 +19,7 @@ from .fused import (GRAD_BLOCKS_DIM_MAX, GRAD_BLOCKS_MAX, GRAM_COLUMNS_MAX, gp, 
 from .batch import (_gp_rows, _lti_table, gp_ll_batch, gp_ll_grad_adj_batch, gp_predict_batch, lti_ll_batch, lti_ll_grad_batch,
                     lti_predict_batch, mix_moments)
 from .series import PackBuffer, Series, _Packed
+from . import panel
+from .panel import PANEL_MAX_STEPS, PanelData, gp_panel_ll, gp_panel_ll_grad, gp_panel_predict
 from .sites import (LIK_BERNOULLI_LOGIT, LIK_GAUSSIAN, LIK_POISSON_EXP, LIK_W_MIN, NEWTON_SUMS, SiteBuffers, gp_newton,
                     lik_sites)

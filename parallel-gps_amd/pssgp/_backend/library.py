@@ -94,6 +94,9 @@ _SIGNATURES = (
     ("pgps_lti_ll_batch{dev}_f64 pgps_lti_ll_grad_batch{dev}_f64", "PILIPPPDP"),
     ("pgps_gp_predict_batch{dev}_{suf} pgps_lti_predict_batch{dev}_f64", "PILLIPPPDPPPP"),
     ("pgps_mix_moments_dev_f64", "PILPPPPP"),
+    # S series at once, each on its own clock
+    ("pgps_gp_panel_ll{dev}_f64 pgps_gp_panel_ll_grad{dev}_f64", "PLPIIPPPPP"),
+    ("pgps_gp_panel_predict{dev}_f64", "PLPPIIPPPPPPPP"),
     # a series kept on the device
     ("pgps_series_create_f64", "PLPPDH"),
     ("pgps_series_set_queries_f64", "PLP"),

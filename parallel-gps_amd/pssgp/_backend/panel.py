@@ -1,0 +1,171 @@
+"""A panel: S independent series, each on its own clock and of its own length, evaluated in one launch per group
+(pgps_gp_panel_*, include/pgps.h; fp64, Matern-family models, d <= 3).  Host-array calls, and PanelData: the concatenated
+series kept on the device across calls, which the *_dev functions run on."""
+import numpy as np
+
+from .arrays import _prep, _ptr
+from .batch import _gp_rows
+from .context import get_context
+from .library import _require
+
+PANEL_MAX_STEPS = 2048          # PGPS_PANEL_MAX_STEPS: steps of one series, counted merged (n + k) in predict
+
+
+def _panel_context(device):
+    return _require(get_context(device), "pgps_gp_panel_ll_f64", "pgps_gp_panel_*")
+
+
+def _offsets(offs, what="offs"):
+    o = np.ascontiguousarray(offs, dtype=np.int64).reshape(-1)
+    if o.shape[0] < 2 or o[0] != 0:
+        raise ValueError(f"{what} must hold S + 1 >= 2 offsets starting at 0, got {o!r}")
+    return o
+
+
+def _table(models, S):
+    """(table, d, nmodels) of `models` as _gp_rows takes them: one row (shared by all series) or S rows."""
+    table, d = _gp_rows(models)
+    if table.shape[0] not in (1, S):
+        raise ValueError(f"a panel of {S} series takes 1 model (shared) or {S}, got {table.shape[0]}")
+    return table, d, table.shape[0]
+
+
+def _inputs(offs, ts, ys, rs):
+    o = _offsets(offs)
+    n = int(o[-1])
+    ts_a, ys_a = _prep(ts, np.float64, (-1,)), _prep(ys, np.float64, (-1,))
+    rs_a = None if rs is None else _prep(rs, np.float64, (-1,))
+    for name, a in (("ts", ts_a), ("ys", ys_a), ("rs", rs_a)):
+        if a is not None and a.shape[0] != n:
+            raise ValueError(f"{name} has {a.shape[0]} rows, offs ends at {n}")
+    return o, ts_a, ys_a, rs_a
+
+
+def gp_panel_ll(models, offs, ts, ys, rs=None, device=0):
+    """Log-likelihoods (S,) of the S series cut out of the concatenated ts, ys (and rs: per-observation noise variances, or None)
+    by `offs` (S + 1,); `models`: 1 or S entries as gp_ll_batch takes them, or their table (pgps_gp_panel_ll_f64)."""
+    o, ts_a, ys_a, rs_a = _inputs(offs, ts, ys, rs)
+    S = o.shape[0] - 1
+    table, d, nm = _table(models, S)
+    ll = np.empty(S, np.float64)
+    _panel_context(device).call("pgps_gp_panel_ll_f64", S, _ptr(o), d, nm, _ptr(table), _ptr(ts_a), _ptr(ys_a), _ptr(rs_a), _ptr(ll))
+    return ll
+
+
+def gp_panel_ll_grad(models, offs, ts, ys, rs=None, device=0):
+    """(S, 1 + d d + 2 d + 1): row s = [ll | Abar | Ubar | Hbar | Rbar] of series s (pgps_gp_panel_ll_grad_f64; split_grad_stats)."""
+    o, ts_a, ys_a, rs_a = _inputs(offs, ts, ys, rs)
+    S = o.shape[0] - 1
+    table, d, nm = _table(models, S)
+    out = np.empty((S, 2 + d * d + 2 * d), np.float64)
+    _panel_context(device).call("pgps_gp_panel_ll_grad_f64", S, _ptr(o), d, nm, _ptr(table), _ptr(ts_a), _ptr(ys_a), _ptr(rs_a),
+                                _ptr(out))
+    return out
+
+
+def gp_panel_predict(models, offs, qoffs, ts, ys, rs, tq, device=0):
+    """predict_f of every series at its own (sorted) queries, rows qoffs[s] .. qoffs[s + 1] of tq (a series may have none):
+    (mean, var (qoffs[S],), ll (S,)) (pgps_gp_panel_predict_f64)."""
+    o, ts_a, ys_a, rs_a = _inputs(offs, ts, ys, rs)
+    q = _offsets(qoffs, "qoffs")
+    S = o.shape[0] - 1
+    tq_a = _prep(tq, np.float64, (-1,))
+    if q.shape[0] != S + 1 or tq_a.shape[0] != int(q[-1]):
+        raise ValueError(f"qoffs must hold {S + 1} offsets ending at the {tq_a.shape[0]} rows of tq, got {q!r}")
+    table, d, nm = _table(models, S)
+    K = tq_a.shape[0]
+    mean, var, ll = np.empty(K, np.float64), np.empty(K, np.float64), np.empty(S, np.float64)
+    _panel_context(device).call("pgps_gp_panel_predict_f64", S, _ptr(o), _ptr(q), d, nm, _ptr(table), _ptr(ts_a), _ptr(ys_a),
+                                _ptr(rs_a), _ptr(tq_a), _ptr(mean), _ptr(var), _ptr(ll))
+    return mean, var, ll
+
+
+class PanelData:
+    """The concatenated series of a panel on the device: ts, ys (and rs) uploaded once, owned by this object and freed with
+    it; the *_dev functions below run the device-pointer entry points on them.  Query grids and results travel per call
+    through buffers that grow as needed and are owned here too."""
+
+    def __init__(self, offs, ts, ys, rs=None, device=0):
+        self.ctx = _panel_context(device)
+        self.offs, ts_a, ys_a, rs_a = _inputs(offs, ts, ys, rs)
+        self.S = self.offs.shape[0] - 1
+        self._bufs = {}
+        self._fixed = []
+        try:
+            self.ts, self.ys = self._upload(ts_a), self._upload(ys_a)
+            self.rs = None if rs_a is None else self._upload(rs_a)
+        except Exception:
+            self.close()
+            raise
+
+    def _upload(self, a):
+        p = self.ctx.malloc(a.nbytes)
+        self._fixed.append(p)
+        self.ctx.h2d(p, a)
+        return p
+
+    def _buffer(self, name, nbytes):
+        """A device buffer of at least nbytes under `name`, grown (never shrunk) across calls."""
+        have = self._bufs.get(name)
+        if have is None or have[1] < nbytes:
+            if have is not None:
+                self.ctx.free(have[0])
+                del self._bufs[name]
+            have = self._bufs[name] = (self.ctx.malloc(nbytes), nbytes)
+        return have[0]
+
+    def close(self):
+        ctx = getattr(self, "ctx", None)
+        if ctx is None or not getattr(ctx.handle, "value", None):
+            return
+        for p in self._fixed + [b[0] for b in self._bufs.values()]:
+            ctx.free(p)
+        self._fixed, self._bufs = [], {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # noqa: BLE001 -- interpreter shutdown
+            pass
+
+
+def gp_panel_ll_dev(data, models):
+    """gp_panel_ll on the resident series of `data` (pgps_gp_panel_ll_dev_f64): (S,)."""
+    table, d, nm = _table(models, data.S)
+    ll = np.empty(data.S, np.float64)
+    with data.ctx.lock:
+        dll = data._buffer("out", ll.nbytes)
+        data.ctx.call("pgps_gp_panel_ll_dev_f64", data.S, _ptr(data.offs), d, nm, _ptr(table), data.ts, data.ys, data.rs, dll)
+        data.ctx.d2h(ll, dll)
+    return ll
+
+
+def gp_panel_ll_grad_dev(data, models):
+    """gp_panel_ll_grad on the resident series of `data` (pgps_gp_panel_ll_grad_dev_f64): (S, 1 + d d + 2 d + 1)."""
+    table, d, nm = _table(models, data.S)
+    out = np.empty((data.S, 2 + d * d + 2 * d), np.float64)
+    with data.ctx.lock:
+        dout = data._buffer("out", out.nbytes)
+        data.ctx.call("pgps_gp_panel_ll_grad_dev_f64", data.S, _ptr(data.offs), d, nm, _ptr(table), data.ts, data.ys, data.rs, dout)
+        data.ctx.d2h(out, dout)
+    return out
+
+
+def gp_panel_predict_dev(data, models, qoffs, tq):
+    """gp_panel_predict on the resident series of `data` (pgps_gp_panel_predict_dev_f64): the queries go up, (mean, var
+    (qoffs[S],), ll (S,)) come back."""
+    q = _offsets(qoffs, "qoffs")
+    tq_a = _prep(tq, np.float64, (-1,))
+    if q.shape[0] != data.S + 1 or tq_a.shape[0] != int(q[-1]):
+        raise ValueError(f"qoffs must hold {data.S + 1} offsets ending at the {tq_a.shape[0]} rows of tq, got {q!r}")
+    table, d, nm = _table(models, data.S)
+    K = tq_a.shape[0]
+    res = np.empty(2 * K + data.S, np.float64)              # [mean | var | ll]: one copy back
+    with data.ctx.lock:
+        dtq = data._buffer("tq", tq_a.nbytes)
+        dres = data._buffer("res", res.nbytes)
+        data.ctx.h2d(dtq, tq_a)
+        data.ctx.call("pgps_gp_panel_predict_dev_f64", data.S, _ptr(data.offs), _ptr(q), d, nm, _ptr(table), data.ts, data.ys,
+                      data.rs, dtq, dres, dres + 8 * K, dres + 16 * K)
+        data.ctx.d2h(res, dres)
+    return res[:K], res[K:2 * K], res[2 * K:]

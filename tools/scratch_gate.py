@@ -17,7 +17,7 @@ import subprocess
 import sys
 
 GATED = ("pgps::rc::", "pgps::rc2::", "pgps::qc::", "pgps::k_pkfs_resident", "pgps::k_sample_", "pgps::k_cov_", "pgps::k_gpm_",
-         "pgps::k_gph_", "pgps::k_gpl_", "pgps::k_gps_")
+         "pgps::k_gph_", "pgps::k_gpl_", "pgps::k_gps_", "pgps::k_gpp_", "pgps::k_panel_")
 
 # units that legitimately hold no gated kernel (their .res may be passed by a glob): rc2_32 -- the two-rows kernels end at
 # d = 23 in fp64 and d = 31 in fp32, the unit only carries the dispatch stubs
