@@ -710,6 +710,47 @@ int pgps_lik_sites_dev_f64(pgps_ctx*, long N, int lik, double par, const double*
                            const double* f_b /* may be NULL */, const double* alpha_b /* may be NULL */, double step,
                            double* f_out, double* alpha_out, double* zs_out, double* ss_out, double* sums /* 3 */);
 
+/* ---- Laplace inference for a panel: the mode search of S series in ONE launch (fused path, fp64, d <= 3) -------
+ * The data of Laplace inference is usually a panel (spike trains of many neurons, counts per patient or sensor): S series cut
+ * out of concatenated ts, ys by offs as the pgps_gp_panel_* calls take them, one likelihood `lik`.  pgps_gp_panel_laplace_*
+ * gives every series ONE workgroup that runs the WHOLE damped Newton search from f = 0 inside the kernel -- start, passes
+ * (the three bodies of pgps_gp_newton_* back to back), halvings, accept, the closing pass -- with its own iteration count;
+ * nothing comes back before the mode is found.  The rule is csrc/pgps_newton.h: a proposal is accepted when its Psi is finite
+ * and >= Psi - 1e-12 |Psi|, else halved (at most 20 times per step); converged when a pass moves f by <= tol; unconverged
+ * after max_iter steps the last iterate is kept.  At most max_iter + 1 passes and 20 max_iter damped updates per series.
+ *   models   the panel's table, nmodels = 1 or S rows [lam | N1 | N2 | Pinf | H | R]; R is IGNORED and taken as 0
+ *   pars     HOST, npars = 1 or S likelihood parameters (Poisson: the exposure of series s; Bernoulli: unused)
+ *   f, v, zs, ss   (offs[S]) each, in the rows' order: the mode, its variances, the sites at the mode (zs NaN and ss 1 at the
+ *            missing rows, as pgps_gp_newton_* leaves them)
+ *   info     (S, 8): [ll_sites | corr | psi | iterations | halvings | converged (0 / 1) | last move | observed rows].  The log of
+ *            the Laplace evidence is ll_sites + corr plus the likelihood's constant, which the caller adds.
+ * pgps_gp_panel_laplace_grad_*: from (f, v, zs, ss) of the call above, the three observation arrays of the identity
+ * grad log q = grad [G(z + w) - G(w) + G(0)], w = v d3 / (2 W), three launches of the panel's adjoint pass with rs = ss, R = 0,
+ * and their combination on the device: out (S, 1 + d d + 2 d + 1) rows [c | Abar | Ubar | Hbar | Rbar] as
+ * pgps_gp_panel_ll_grad_* lays them out.  The first column c is the COMBINATION G(z + w) - G(w) + G(0), not the evidence.
+ * Prediction needs no entry point of its own: pgps_gp_panel_predict_dev_f64 with ys = zs, rs = ss and R = 0 in the table.
+ * Host forms take host arrays and return PGPS_E_NUMERIC where an info row (the first column of an out row) is not finite;
+ * _dev forms take device pointers for everything but offs / models / pars, synchronise the context's stream ONCE to copy their
+ * tables in and are asynchronous afterwards.  Steps per lane, groups and bit-repeatability as the pgps_gp_panel_* calls.
+ * Profiling: the search kernel has no timer slot of its own.  pgps_profile_* charge a whole search (and the gradient's input
+ * kernel) to PGPS_K_SMOOTHER_APPLY, the adjoint passes to PGPS_K_FILTER_APPLY and the combination to PGPS_K_LL_FINALIZE; the
+ * roctx ranges are "laplace_panel_search" and "laplace_panel_grad".
+ * Errors (no output is touched): S < 1, a null pointer, an empty series, a series above PGPS_PANEL_MAX_STEPS, nmodels or npars
+ * not 1 or S, lam <= 0 in a row, an unknown lik, a Gaussian or Poisson par that is not finite and > 0, tol not finite or < 0,
+ * max_iter outside 1 .. 1000: PGPS_E_INVALID; d outside 1..3: PGPS_E_UNSUPPORTED_DIM. */
+int pgps_gp_panel_laplace_f64(pgps_ctx*, long S, const long* offs, int d, int nmodels, const double* models, int lik, int npars,
+                              const double* pars, const double* ts, const double* ys, double tol, int max_iter, double* f,
+                              double* v, double* zs, double* ss, double* info /* S 8 */);
+int pgps_gp_panel_laplace_dev_f64(pgps_ctx*, long S, const long* offs, int d, int nmodels, const double* models, int lik,
+                                  int npars, const double* pars, const double* ts, const double* ys, double tol, int max_iter,
+                                  double* f, double* v, double* zs, double* ss, double* info /* S 8 */);
+int pgps_gp_panel_laplace_grad_f64(pgps_ctx*, long S, const long* offs, int d, int nmodels, const double* models, int lik,
+                                   int npars, const double* pars, const double* ts, const double* ys, const double* f,
+                                   const double* v, const double* zs, const double* ss, double* out);
+int pgps_gp_panel_laplace_grad_dev_f64(pgps_ctx*, long S, const long* offs, int d, int nmodels, const double* models, int lik,
+                                       int npars, const double* pars, const double* ts, const double* ys, const double* f,
+                                       const double* v, const double* zs, const double* ss, double* out);
+
 /* ---- sequential mode: pssgp/kalman/sequential.py:11-73 (kf, ks) ------------------------
  * StateSpaceGP(parallel=False).  Host arithmetic on HOST pointers, as in the reference (its
  * sequential mode is the CPU `tf.scan`).  No context needed.  mps / Pps (predicted moments,

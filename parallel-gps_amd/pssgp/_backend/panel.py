@@ -169,3 +169,117 @@ def gp_panel_predict_dev(data, models, qoffs, tq):
                       data.rs, dtq, dres, dres + 8 * K, dres + 16 * K)
         data.ctx.d2h(res, dres)
     return res[:K], res[K:2 * K], res[2 * K:]
+
+
+# -- Laplace inference on a panel (pgps_gp_panel_laplace_*) ---------------------------------------------
+PANEL_INFO = ("ll_sites", "correction", "psi", "iterations", "halvings", "converged", "max_move", "n_obs")
+NEWTON_MAX_ITER_CAP = 1000      # kNewtonMaxIterCap of csrc/pgps_newton.h
+
+
+def _laplace_context(device):
+    return _require(get_context(device), "pgps_gp_panel_laplace_f64", "pgps_gp_panel_laplace_*")
+
+
+def _pars(pars, S):
+    p = np.ascontiguousarray(pars, dtype=np.float64).reshape(-1)
+    if p.shape[0] not in (1, S):
+        raise ValueError(f"a panel of {S} series takes 1 likelihood parameter (shared) or {S}, got {p.shape[0]}")
+    return p
+
+
+def gp_panel_laplace(models, lik, pars, offs, ts, ys, tol=1e-8, max_iter=50, device=0):
+    """The mode search of every series of a panel in one launch per group (pgps_gp_panel_laplace_f64), host arrays: a dict
+    with "f", "v", "zs", "ss" (offs[S],) -- the modes, their variances, the sites at them -- and "info" (S, 8) in the order
+    of PANEL_INFO.  `models` as gp_panel_ll takes them (R is ignored); `pars`: 1 or S likelihood parameters."""
+    o, ts_a, ys_a, _ = _inputs(offs, ts, ys, None)
+    S = o.shape[0] - 1
+    table, d, nm = _table(models, S)
+    p = _pars(pars, S)
+    n = int(o[-1])
+    out = {k: np.empty(n, np.float64) for k in ("f", "v", "zs", "ss")}
+    out["info"] = np.empty((S, len(PANEL_INFO)), np.float64)
+    _laplace_context(device).call("pgps_gp_panel_laplace_f64", S, _ptr(o), d, nm, _ptr(table), int(lik), p.shape[0], _ptr(p),
+                                  _ptr(ts_a), _ptr(ys_a), float(tol), int(max_iter),
+                                  *(_ptr(out[k]) for k in ("f", "v", "zs", "ss", "info")))
+    return out
+
+
+def gp_panel_laplace_grad(models, lik, pars, offs, ts, ys, f, v, zs, ss, device=0):
+    """(S, 1 + d d + 2 d + 1): row s = [c | Abar | Ubar | Hbar | Rbar], the adjoint statistics of the evidence of series s at the
+    mode gp_panel_laplace returned (pgps_gp_panel_laplace_grad_f64; split_grad_stats).  c is the combination
+    G(z + w) - G(w) + G(0), not the evidence."""
+    o, ts_a, ys_a, _ = _inputs(offs, ts, ys, None)
+    S = o.shape[0] - 1
+    table, d, nm = _table(models, S)
+    p = _pars(pars, S)
+    rows = [_prep(a, np.float64, (-1,)) for a in (f, v, zs, ss)]
+    if any(a.shape[0] != int(o[-1]) for a in rows):
+        raise ValueError(f"f, v, zs, ss must have the panel's {int(o[-1])} rows")
+    out = np.empty((S, 2 + d * d + 2 * d), np.float64)
+    _laplace_context(device).call("pgps_gp_panel_laplace_grad_f64", S, _ptr(o), d, nm, _ptr(table), int(lik), p.shape[0],
+                                  _ptr(p), _ptr(ts_a), _ptr(ys_a), *(_ptr(a) for a in rows), _ptr(out))
+    return out
+
+
+def _site_rows(data):
+    """The device addresses of f, v, zs, ss of `data`: one buffer the panel keeps between the fit, the gradient and predict."""
+    n = int(data.offs[-1])
+    base = data._buffer("sites", 4 * 8 * n)
+    return [base + 8 * n * i for i in range(4)]
+
+
+def gp_panel_laplace_dev(data, models, lik, pars, tol=1e-8, max_iter=50, rows=False):
+    """gp_panel_laplace on the resident series of `data` (pgps_gp_panel_laplace_dev_f64).  f, v, zs, ss stay on the device in
+    `data` for gp_panel_laplace_grad_dev / gp_panel_laplace_predict_dev; info (S, 8) comes back, and with rows=True the
+    dict of gp_panel_laplace."""
+    _require(data.ctx, "pgps_gp_panel_laplace_dev_f64", "pgps_gp_panel_laplace_*")
+    table, d, nm = _table(models, data.S)
+    p = _pars(pars, data.S)
+    info = np.empty((data.S, len(PANEL_INFO)), np.float64)
+    n = int(data.offs[-1])
+    with data.ctx.lock:
+        f, v, zs, ss = _site_rows(data)
+        dinfo = data._buffer("info", info.nbytes)
+        data.ctx.call("pgps_gp_panel_laplace_dev_f64", data.S, _ptr(data.offs), d, nm, _ptr(table), int(lik), p.shape[0], _ptr(p),
+                      data.ts, data.ys, float(tol), int(max_iter), f, v, zs, ss, dinfo)
+        data.ctx.d2h(info, dinfo)
+        if not rows:
+            return info
+        back = np.empty(4 * n, np.float64)
+        data.ctx.d2h(back, f)
+    return {"f": back[:n], "v": back[n:2 * n], "zs": back[2 * n:3 * n], "ss": back[3 * n:], "info": info}
+
+
+def gp_panel_laplace_grad_dev(data, models, lik, pars):
+    """gp_panel_laplace_grad on the modes gp_panel_laplace_dev left in `data` (pgps_gp_panel_laplace_grad_dev_f64)."""
+    table, d, nm = _table(models, data.S)
+    p = _pars(pars, data.S)
+    out = np.empty((data.S, 2 + d * d + 2 * d), np.float64)
+    with data.ctx.lock:
+        f, v, zs, ss = _site_rows(data)
+        dout = data._buffer("out", out.nbytes)
+        data.ctx.call("pgps_gp_panel_laplace_grad_dev_f64", data.S, _ptr(data.offs), d, nm, _ptr(table), int(lik), p.shape[0],
+                      _ptr(p), data.ts, data.ys, f, v, zs, ss, dout)
+        data.ctx.d2h(out, dout)
+    return out
+
+
+def gp_panel_laplace_predict_dev(data, models, qoffs, tq):
+    """The posterior of f under the approximation at every series' queries: pgps_gp_panel_predict_dev_f64 on the sites
+    gp_panel_laplace_dev left in `data` (ys = zs, rs = ss; the table's R must be 0).  (mean, var (qoffs[S],))."""
+    q = _offsets(qoffs, "qoffs")
+    tq_a = _prep(tq, np.float64, (-1,))
+    if q.shape[0] != data.S + 1 or tq_a.shape[0] != int(q[-1]):
+        raise ValueError(f"qoffs must hold {data.S + 1} offsets ending at the {tq_a.shape[0]} rows of tq, got {q!r}")
+    table, d, nm = _table(models, data.S)
+    K = tq_a.shape[0]
+    res = np.empty(2 * K, np.float64)
+    with data.ctx.lock:
+        _, _, zs, ss = _site_rows(data)
+        dtq = data._buffer("tq", tq_a.nbytes)
+        dres = data._buffer("res", res.nbytes)
+        data.ctx.h2d(dtq, tq_a)
+        data.ctx.call("pgps_gp_panel_predict_dev_f64", data.S, _ptr(data.offs), _ptr(q), d, nm, _ptr(table), data.ts, zs, ss, dtq,
+                      dres, dres + 8 * K, None)
+        data.ctx.d2h(res, dres)
+    return res[:K], res[K:]
