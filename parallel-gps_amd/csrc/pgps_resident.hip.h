@@ -622,6 +622,37 @@ struct ResLaneValues {
     }
 };
 
+// The lane's smoothing aggregate e_0 (x) e_1 (x) ... (x) e_{LC-1}, strictly left to right, is folded INSIDE the Kalman pass: it
+// is independent of the pass's own chain (m, P) and fills issue slots that chain leaves empty.  Nothing but the suffix scan
+// behind the pass reads it, so without a pin the compiler sinks all LC combines there, out of the unrolled steps and across
+// their sched_barriers, onto the stretch the left neighbour waits for.  With 16 steps per lane an element
+// joins the chain one step AFTER the step that computes it, when its operands are long ready (the last two behind the
+// loop); with 8 in its own step: chosen per LC by measurement (profiles/resident_aggregate_placements.txt).
+// The chain starts AT its first element: smth_combine(identity, e) returns e bit for bit (tests/test_res_identity.py,
+// tests/test_gpu_resident_aggregate.py).
+template <int LC> struct ResAggLate { static constexpr bool value = LC >= 16; };
+template <typename T, int D>
+__device__ __forceinline__ void res_pin(SmthElem<T, D>& e) {
+#pragma unroll
+    for (int i = 0; i < D * D; ++i) asm volatile("" : "+v"(e.E[i]));
+#pragma unroll
+    for (int i = 0; i < D; ++i) asm volatile("" : "+v"(e.g[i]));
+#pragma unroll
+    for (int i = 0; i < Dim<D>::SYM; ++i) asm volatile("" : "+v"(e.L[i]));
+}
+// sagg <- sagg (x) e (the chain's first link: sagg <- e), kept where it is written
+template <typename T, int D>
+__device__ __forceinline__ void res_agg_fold(SmthElem<T, D>& sagg, const SmthElem<T, D>& e, bool first) {
+    if (first) {
+        sagg = e;
+    } else {
+        SmthElem<T, D> r;
+        smth_combine(sagg, e, r);
+        sagg = r;
+    }
+    res_pin(sagg);
+}
+
 // SMOOTH = false: the filter alone (pkf: filtered moments and / or the log-likelihood) -- phases 1 and 2 without the smoothing
 // elements, one hand-off; the series still stays on chip between the reduce and the Kalman pass, i.e. Fs, Qs, ys are read once.
 template <typename T, int D, int LC, bool FUSED, bool SMOOTH = true, bool SKEW = false>
@@ -850,8 +881,10 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
     PGPS_RSTAMP(4);
 
     LogLik ll;
-    SE sagg;
+    constexpr bool AGG_LATE = ResAggLate<LC>::value;
+    SE sagg, epend;             // the lane's aggregate; AGG_LATE: the element that joins it in the next step
     smth_identity(sagg);
+    smth_identity(epend);
     // F, Q of the step after the chunk: the next lane's first step (its registers / its slot); the wave's last lane
     // reads global memory (the next wave's or workgroup's first step), or pads
     T Fh[MAT], Qh[MAT];
@@ -925,10 +958,14 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
 #endif
                 if constexpr (SMOOTH) {
                     // element of step j - 1: E, g take the registers F_{j-1}, y_{j-1} have left; L waits for its slot
-                    SE e, r;
+                    SE e;
                     element(j, prev, mp, Pp, FP, e);
-                    smth_combine(sagg, e, r);
-                    sagg = r;
+                    if constexpr (AGG_LATE) {
+                        if (j >= 2) res_agg_fold(sagg, epend, j == 2);
+                        epend = e;
+                    } else {
+                        res_agg_fold(sagg, e, j == 1);
+                    }
 #pragma unroll
                     for (int q = 0; q < MAT; ++q) Freg[j - 1][q] = e.E[q];
                     yreg[j - 1] = e.g[D - 1];
@@ -1001,10 +1038,10 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
         sym_from_full<T, D>(Qh, Q);
         mat_vec<T, D>(Fh, s.m, mp);
         predict_cov<T, D>(Fh, s.P, Q, FP, Pp);
-        SE e, r;
+        SE e;
         element(LC, s, mp, Pp, FP, e);
-        smth_combine(sagg, e, r);
-        sagg = r;
+        if constexpr (AGG_LATE) res_agg_fold(sagg, epend, false);
+        res_agg_fold(sagg, e, false);
 #pragma unroll
         for (int q = 0; q < MAT; ++q) Freg[j][q] = e.E[q];
         yreg[j] = e.g[D - 1];
@@ -1023,6 +1060,8 @@ __global__ __launch_bounds__(kBlock) void k_pkfs_resident(const ResArgs<T> ra) {
     }
     PGPS_RSTAMP_WAVE(1);
     PGPS_RSTAMP(5);
+    // (diagnostics: whatever of the aggregate's chain is left behind the pass stands between stamps 5 and 14)
+    PGPS_RSTAMP(14);
     SE sexcl;
     // the smoothing total first, from inside the scan (wave 0; its lane 0 holds it): the left neighbour waits for it alone
     res_block_scan_exclusive<SE, false>(sagg, sexcl, lds, [&](const SE& stotal) {

@@ -7,8 +7,9 @@ array entry point always returns them) -- what the pass costs without its stores
 
 Stamps (slots of resident_stamps(), wave 0 lane 0): 0 start, 1 reduce done, 2 forward scan done (and, where the total is
 published from inside the scan, published), 3 carry in, 4 applied, 5 Kalman pass + last element done, 6 suffix scan done,
-7 carry in, 8 applied, 9 end.  The rows "scan ... wait" are the part of the launch in which the memory path idles:
-(3 - 1) + (7 - 5)."""
+7 carry in, 8 applied, 9 end; 14 (between 5 and 6) the head of the suffix scan: 5 -> 14 is whatever of the lane's smoothing
+aggregate the compiler has left behind the Kalman pass, 14 -> 6 the scan itself.  The rows "scan ... wait"
+are the part of the launch in which the memory path idles: (3 - 1) + (7 - 5)."""
 import argparse
 import os
 import sys
@@ -29,6 +30,10 @@ def table(st, ws):
             ("fold+apply", d(3, 4)), ("kalman pass", d(4, 5)), ("suffix scan (+publish)", d(5, 6)),
             ("ll + wait right neighbour", d(6, 7)), ("fold+apply", d(7, 8)), ("rts pass", d(8, 9))]
     out = [f"    {n:28s} {v:9.0f}" for n, v in rows]
+    if np.all((st[:, 14] >= st[:, 5]) & (st[:, 14] <= st[:, 6])):
+        # libraries with the diagnostic stamp in front of the suffix scan (slot 14): what stands between the pass and the scan
+        out[6:6] = [f"    {'  aggregate block (5->14)':28s} {d(5, 14):9.0f}", f"    {'  scan proper (14->6)':28s} {d(14, 6):9.0f}",
+                    f"    {'kalman + aggregate + suffix':28s} {d(4, 6):9.0f}"]
     out.append(f"    {'scan + hand-off (1->3, 5->7)':28s} {d(1, 3) + d(5, 7):9.0f}")
     out.append(f"    {'total':28s} {d(0, 9):9.0f}")
     if ws is not None:
