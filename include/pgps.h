@@ -666,6 +666,24 @@ int pgps_gp_loo_dev_f64(pgps_ctx*, long N, int d, double lam, const double* N1, 
                         const double* H, double R, const double* ts, const double* ys, double t0, double* osa_mean,
                         double* osa_var, double* loo_mean, double* loo_var, double* sums /* 2 */);
 
+/* ---- ... of every series of a panel, in one launch per group ------------------------------------------
+ * offs, models, rs, PGPS_PANEL_MAX_STEPS and the host / device conventions are those of pgps_gp_panel_ll_*; the four arrays hold
+ * one value per row of the concatenated series (offs[S] doubles), each may be NULL; sums (S, 2) = {ll, loo_lpd} per series is
+ * always written.  Row s is what pgps_gp_loo_* computes on series s alone (t0 = the series' first time), with the step's noise
+ * variance R + rs[k] where rs is given.  At a row where ys is NaN the stored variances are ... + R + rs[k] with rs[k] AS STORED (a
+ * NaN there gives a NaN variance at that row only; it never enters the recursions).  A row's bits depend on that series alone
+ * (the list at pgps_gp_panel_ll_*), and they do not change when arrays are NULL.
+ * Errors (no output is touched): those of pgps_gp_panel_ll_*, among them R <= 0 in a row when rs is NULL, and a null sums:
+ * PGPS_E_INVALID; d outside 1..3: PGPS_E_UNSUPPORTED_DIM.  The host form scans rs once (finite, >= 0 and R + rs[k] > 0 at the
+ * observed rows, else PGPS_E_INVALID: a PRECONDITION of the _dev form), copies back only the arrays asked for and returns
+ * PGPS_E_NUMERIC on a non-finite sum. */
+int pgps_gp_panel_loo_f64(pgps_ctx*, long S, const long* offs, int d, int nmodels, const double* models, const double* ts,
+                          const double* ys, const double* rs, double* osa_mean, double* osa_var, double* loo_mean,
+                          double* loo_var, double* sums /* (S, 2) */);
+int pgps_gp_panel_loo_dev_f64(pgps_ctx*, long S, const long* offs, int d, int nmodels, const double* models, const double* ts,
+                              const double* ys, const double* rs, double* osa_mean, double* osa_var, double* loo_mean,
+                              double* loo_var, double* sums /* (S, 2) */);
+
 /* ---- Laplace inference for non-Gaussian observations (fused path, fp64, d <= 3) -------------------------
  * Observations y_k ~ p(y | f(t_k)) with a log-concave likelihood, `lik` one of PGPS_LIK_* with one parameter `par` (csrc/
  * pgps_lik.h: lp = log p, g = lp', W = -lp'' floored at 1e-10, d3 = lp''').  A SITE formed at f is the Gaussian factor

@@ -99,20 +99,26 @@ __device__ __forceinline__ void gp_apply_step_r(const ScanArgs<T>& a, long k, lo
 // not).  LOO (gp_smooth_body): the smoother projects at every step, reads y_k and removes the factor N(y_k | f_k, R) from the
 // smoothed law of f_k = H x_k (Rasmussen & Williams eq. 5.10-5.12 in cavity form), stores the leave-one-out law of y_k and
 // accumulates its log density; one partial per workgroup (lpd_part), summed afterwards in a fixed order.  Any of the four
-// arrays of GpLooOut (pgps_internal.h) may be null: that store is skipped.  Instantiated in pgps_loo_inst.hip only.
+// arrays of GpLooOut (pgps_internal.h) may be null: that store is skipped.  Instantiated in pgps_loo_inst.hip and, one
+// workgroup per series, in pgps_panel_inst.hip (k_gpp_loo).
+// Both flavours combine with per-observation noise, again at compile time and off by default: OSA + HET
+// takes the step's variance R_k = het_noise(R, rs[k], y_k) into the recursion and stores S_k with R + rs[k] AS STORED (at a
+// missing row a NaN there gives a NaN variance at that row and reaches nothing else); LHET (gp_smooth_body, with LOO) loads
+// rs[k - 1] next to ys[k - 1], under the same guard, and the epilogue removes N(y_k | f_k, R + rs[k]).
 // ---------------------------------------------------------------------------------------------
-// gp_apply_step_r that also hands out (mu, S) of the step: kf_step's own expressions on the predicted moments it returns
+// gp_apply_step_r that also hands out (mu, S) of the step: kf_step's own expressions on the predicted moments it returns.
+// R: the step's noise variance in the recursion; Rs: the one in the stored S (they differ at a missing row of HET alone)
 template <typename T, int D, bool SMOOTH>
 __device__ __forceinline__ void gp_apply_step_osa(const ScanArgs<T>& a, long k, long k0, const T* F, const T* Qf, T y, const T* h,
-                                                  MeanCov<T, D>& s, LogLik& ll, SmthElem<T, D>& sagg, T& mu, T& S) {
+                                                  T R, T Rs, MeanCov<T, D>& s, LogLik& ll, SmthElem<T, D>& sagg, T& mu, T& S) {
     constexpr int MAT = D * D, SYM = Dim<D>::SYM;
     T Q[SYM];
     sym_from_full<T, D>(Qf, Q);
     T mp[D], Pp[SYM], FP[MAT], u[D];
     MeanCov<T, D> prev = s;
-    kf_step(s, F, Q, y, h, a.R, (k == 0) && a.seg_first, ll, mp, Pp, FP);
+    kf_step(s, F, Q, y, h, R, (k == 0) && a.seg_first, ll, mp, Pp, FP);
     sym_vec<T, D, kPkStep>(Pp, h, u);
-    S = dot_add<T, D, kPkStep>(h, u, a.R);
+    S = dot_add<T, D, kPkStep>(h, u, Rs);
     mu = dot_add<T, D, kPkStep>(h, mp, T(0));
     if (SMOOTH && k > k0) {                 // element of step k-1 from this step's predict
         SmthElem<T, D> e, r;
@@ -348,8 +354,12 @@ __device__ __forceinline__ void gp_apply_body(const GpArgs<T>& g, GpLds<T, D>& s
             lti_step<T, D>(g.m, t - tprev, F, Qf);
             tprev = t;
             if constexpr (OSA) {
-                T mu, S;
-                gp_apply_step_osa<T, D, SMOOTH>(a, k, k0, F, Qf, y, h, s, ll, sagg, mu, S);
+                T mu, S, Rk = a.R, Rs = a.R;
+                if constexpr (HET) {
+                    Rk = het_noise(a.R, rk, y);
+                    Rs = a.R + rk;
+                }
+                gp_apply_step_osa<T, D, SMOOTH>(a, k, k0, F, Qf, y, h, Rk, Rs, s, ll, sagg, mu, S);
                 if (lo.osa_mean) lo.osa_mean[k] = mu;
                 if (lo.osa_var) lo.osa_var[k] = S;
             } else if constexpr (HET) gp_apply_step_r<T, D, SMOOTH>(a, k, k0, F, Qf, y, h, het_noise(a.R, rk, y), s, ll, sagg);
@@ -472,9 +482,10 @@ static __global__ __launch_bounds__(kBlock) void k_gpb_finalize(const double* ll
 // ---------------------------------------------------------------------------------------------
 // smoother apply
 // ---------------------------------------------------------------------------------------------
-template <typename T, int D, bool NT, bool PROJ = false, bool LOO = false, bool SITE = false>
+template <typename T, int D, bool NT, bool PROJ = false, bool LOO = false, bool SITE = false, bool LHET = false>
 __device__ __forceinline__ void gp_smooth_body(const GpArgs<T>& g, GpLds<T, D>& sh, const GpLooOut<T>& lo = GpLooOut<T>{},
-                                               const GpSiteOut<T>& so = GpSiteOut<T>{}) {
+                                               const GpSiteOut<T>& so = GpSiteOut<T>{}, const T* rs = nullptr) {
+    static_assert(!LHET || LOO, "LHET is a flavour of the leave-one-out epilogue");
     constexpr int MAT = D * D, SYM = Dim<D>::SYM, NS = Dim<D>::NSMTH, G = 4;
     using SE = SmthElem<T, D>;
     using MC = MeanCov<T, D>;
@@ -511,7 +522,7 @@ __device__ __forceinline__ void gp_smooth_body(const GpArgs<T>& g, GpLds<T, D>& 
         stage_issue<GM>(gM + (long)(S - 1) * GM::SEG, pitchM, rM);
     }
     T tnext = T(0), tcur = T(0);
-    [[maybe_unused]] T ycur = T(0);
+    [[maybe_unused]] T ycur = T(0), rcur = T(0);         // (rcur: LHET, the step's given variance, loaded as ycur is)
     [[maybe_unused]] LogLik lpd;
     // SITE: the step's site (a.ys = zs, so.ss), its observation and the previous iterate, loaded a step ahead as ycur is
     [[maybe_unused]] T scur = T(0), ocur = T(0), pcur = T(0);
@@ -522,6 +533,7 @@ __device__ __forceinline__ void gp_smooth_body(const GpArgs<T>& g, GpLds<T, D>& 
         tnext = (k1 < a.N) ? g.m.ts[k1] : T(0);
         tcur = g.m.ts[k1 - 1];
         if constexpr (LOO || SITE) ycur = a.ys[k1 - 1];
+        if constexpr (LHET) rcur = rs[k1 - 1];
         if constexpr (SITE) {
             scur = so.ss[k1 - 1];
             ocur = so.ys[k1 - 1];
@@ -569,8 +581,12 @@ __device__ __forceinline__ void gp_smooth_body(const GpArgs<T>& g, GpLds<T, D>& 
             const T t = tcur;
             if (k > 0) tcur = g.m.ts[k - 1];
             [[maybe_unused]] const T y = ycur;
+            [[maybe_unused]] const T rk = rcur;
             if constexpr (LOO || SITE) {
-                if (k > k0) ycur = a.ys[k - 1];
+                if (k > k0) {
+                    ycur = a.ys[k - 1];
+                    if constexpr (LHET) rcur = rs[k - 1];
+                }
             }
             [[maybe_unused]] const T sk = scur, ok = ocur, pk = pcur;
             if constexpr (SITE) {
@@ -589,7 +605,9 @@ __device__ __forceinline__ void gp_smooth_body(const GpArgs<T>& g, GpLds<T, D>& 
                 // the leave-one-out law of y_k at every step; sms / sPs are not written
                 T m, v, mean, var;
                 gp_project<T, D>(g.m, s, m, v);
-                loo_step(m, v, a.R, y, mean, var, lpd);
+                T Rk = a.R;
+                if constexpr (LHET) Rk = a.R + rk;          // (as stored: a missing row's variance is v + R + rs[k])
+                loo_step(m, v, Rk, y, mean, var, lpd);
                 if (lo.loo_mean) lo.loo_mean[k] = mean;
                 if (lo.loo_var) lo.loo_var[k] = var;
                 continue;

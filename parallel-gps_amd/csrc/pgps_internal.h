@@ -416,8 +416,10 @@ struct PanelCall {
     double *mean, *var;         // predict
     double* ll;                 // (S,)
     double* out;                // gradient: (S, 1 + d^2 + 2 d + 1)
+    double *osa_mean, *osa_var, *loo_mean, *loo_var;    // predictive checks: (offs[S],) each, or null
+    double* sums;               // predictive checks: (S, 2) {ll, loo_lpd}
 };
-enum PanelWhat { PANEL_LL = 0, PANEL_GRAD = 1, PANEL_PREDICT = 2 };
+enum PanelWhat { PANEL_LL = 0, PANEL_GRAD = 1, PANEL_PREDICT = 2, PANEL_LOO = 3 };
 // lays the series out in groups that fit the context's batch budget, copies the two tables in (ONE stream synchronisation),
 // then merge (predict) and one launch per group.  The caller has checked the arguments
 template <int D>

@@ -16,10 +16,14 @@
 //                        gp_smooth_body   ts[k1]               only where k1 < N;     ts[k - 1] where k > 0
 //                        gp_gfwd_body     ts / ys / rs[k + 1]  only where k + 1 < k1
 //                        gp_gback_body    ts[k - 1]            only where k > 0;      ys / rs[k], xs of its own steps
+//                        gp_apply_body    (OSA) the same reads; stores osa_mean / osa_var[k] of its own steps k0 <= k < k1
+//                        gp_smooth_body   (LOO, LHET) ys / rs[k1 - 1] where k0 < k1;  ys / rs[k - 1] only where k > k0;
+//                                         stores loo_mean / loo_var[k] of its own steps
 //                      (read off the bodies as they stand; tests/test_gpu_panel.py gives every series its own seed, so a read of
 //                      a neighbour's row moves a result)
 //   k_gpp_one          reduce, Kalman pass and (predict) projecting smoother back to back, one workgroup per series
 //   k_gpp_gone         reduce, adjoint forward, adjoint backward: out[s] = [ll | Abar | Ubar | Hbar | Rbar]
+//   k_gpp_loo          reduce, Kalman pass (OSA), smoother (LOO): the predictive checks, sums[s] = {ll, loo_lpd}
 //   k_panel_merge      (pgps_panel_inst.hip) merge_sorted_body per series
 //
 // These are also the first one-workgroup forms of the HET bodies (per-observation noise variances): HET is a
@@ -126,6 +130,45 @@ __global__ __launch_bounds__(kBlock) void k_gpp_gone(const PanelArgs p) {
         ga.out[0] = ga.g.s.llpart[0];
 #pragma unroll
         for (int i = 0; i < NST; ++i) ga.out[1 + i] = ga.gpart[i];
+    }
+}
+
+// The predictive checks of every series: reduce, the Kalman pass in its OSA flavour (it keeps the
+// filtered moments: EVERY series has fms / fPs slices of its own n rows in this call) and the smoother in its LOO flavour, one
+// workgroup per series.  The view is that of the training rows (never merged); the four per-row outputs are indexed from the
+// series' row0 in arrays over the concatenated rows, any of them may be null.  nblocks = 1: the workgroup's llpart[0] and
+// lpd_part[0] are the series' totals.
+struct PanelLooArgs {
+    PanelArgs p;                // desc, models, ts, ys, rs, the scan records, fms / fPs, llpart, status; ll is null
+    GpLooOut<double> o;         // the call's arrays (all rows of the call); lpd_part: the group's scratch, one word per slot
+    double* sums;               // (the group's series, 2): {ll, loo_lpd}
+};
+
+template <int D, bool HET>
+__global__ __launch_bounds__(kBlock) void k_gpp_loo(const PanelLooArgs l) {
+    __shared__ GpLds<double, D> sh;
+    const PanelDesc r = l.p.desc[blockIdx.y];
+    const double* rs;
+    GpArgs<double> g = gp_panel_select<D, HET>(l.p, r, false, &rs);
+    g.s.fms = l.p.fms + r.o_fm;
+    g.s.fPs = l.p.fPs + r.o_fP;
+    GpLooOut<double> o;
+    o.osa_mean = l.o.osa_mean ? l.o.osa_mean + r.row0 : nullptr;
+    o.osa_var = l.o.osa_var ? l.o.osa_var + r.row0 : nullptr;
+    o.loo_mean = l.o.loo_mean ? l.o.loo_mean + r.row0 : nullptr;
+    o.loo_var = l.o.loo_var ? l.o.loo_var + r.row0 : nullptr;
+    o.lpd_part = l.o.lpd_part + r.slot;
+    gp_reduce_body<double, D, HET>(g, sh.lds, rs);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    gp_apply_body<double, D, true, false, HET, true>(g, sh, rs, o);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    gp_smooth_body<double, D, false, false, true, false, HET>(g, sh, o, GpSiteOut<double>{}, rs);
+    if (threadIdx.x == 0) {                     // (this lane wrote both partials)
+        double* out = l.sums + 2 * (long)blockIdx.y;
+        out[0] = g.s.llpart[0];
+        out[1] = o.lpd_part[0];
     }
 }
 

@@ -1,5 +1,5 @@
 // pgps_panel_api.hip -- the panel entry points of the C ABI (include/pgps.h: pgps_gp_panel_ll_*, pgps_gp_panel_ll_grad_*,
-// pgps_gp_panel_predict_*): S independent series cut out of concatenated arrays by `offs`, each on its
+// pgps_gp_panel_predict_*, pgps_gp_panel_loo_*; DESIGN.md sections 4aa, 4ac): S independent series cut out of concatenated arrays by `offs`, each on its
 // own clock.  Argument checks, the one scan of `rs` the host forms make, staging through the context's buffers (rs travels
 // behind ys in the same buffer), dispatch to launch_gp_panel<d> (pgps_panel_inst.hip).
 #include "pgps_host.h"
@@ -188,4 +188,51 @@ extern "C" int pgps_gp_panel_predict_f64(pgps_ctx* ctx, long S, const long* offs
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (ll) memcpy(ll, llh.data(), (size_t)S * sizeof(double));
     return panel_rows_finite(S, 1, llh.data());
+}
+
+// ---- predictive checks of every series ----------------------------------------------------------------
+extern "C" int pgps_gp_panel_loo_dev_f64(pgps_ctx* ctx, long S, const long* offs, int d, int nmodels, const double* models,
+                                         const double* ts, const double* ys, const double* rs, double* osa_mean, double* osa_var,
+                                         double* loo_mean, double* loo_var, double* sums) {
+    TRY(panel_check(ctx, S, offs, nullptr, false, d, nmodels, models, ts, ys, rs != nullptr));
+    if (!sums) return PGPS_E_INVALID;
+    std::vector<double> packed;
+    panel_pack_models(nmodels, d, models, packed);
+    PanelCall c{};
+    c.S = S; c.offs = offs; c.nmodels = nmodels; c.models = packed.data(); c.ts = ts; c.ys = ys; c.rs = rs;
+    c.osa_mean = osa_mean; c.osa_var = osa_var; c.loo_mean = loo_mean; c.loo_var = loo_var; c.sums = sums;
+    return panel_dev(ctx, d, c, PANEL_LOO);
+}
+
+extern "C" int pgps_gp_panel_loo_f64(pgps_ctx* ctx, long S, const long* offs, int d, int nmodels, const double* models,
+                                     const double* ts, const double* ys, const double* rs, double* osa_mean, double* osa_var,
+                                     double* loo_mean, double* loo_var, double* sums) {
+    TRY(panel_check(ctx, S, offs, nullptr, false, d, nmodels, models, ts, ys, rs != nullptr));
+    if (!sums) return PGPS_E_INVALID;
+    if (rs && !panel_noise_valid(S, offs, d, nmodels, models, ys, rs)) return PGPS_E_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t N = (size_t)offs[S];
+    std::vector<double> packed;
+    panel_pack_models(nmodels, d, models, packed);
+    PanelCall c{};
+    c.S = S; c.offs = offs; c.nmodels = nmodels; c.models = packed.data();
+    TRY(panel_stage_series(ctx, offs[S], ts, ys, rs, &c));
+    // the arrays asked for leave through ONE staging buffer (none: the sums alone come back)
+    double* host[4] = {osa_mean, osa_var, loo_mean, loo_var};
+    double* dev[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t wanted = 0;
+    for (double* h : host) wanted += h ? 1 : 0;
+    double* dout = nullptr;
+    if (wanted) TRY(stage_in<double>(ctx, ctx->st[7], nullptr, wanted * N, &dout));
+    for (size_t i = 0, j = 0; i < 4; ++i)
+        if (host[i]) dev[i] = dout + (j++) * N;
+    c.osa_mean = dev[0]; c.osa_var = dev[1]; c.loo_mean = dev[2]; c.loo_var = dev[3];
+    TRY(stage_in<double>(ctx, ctx->st[9], nullptr, 2 * (size_t)S, &c.sums));
+    TRY(panel_dev(ctx, d, c, PANEL_LOO));
+    for (int i = 0; i < 4; ++i) TRY(stage_out(ctx, host[i], dev[i], N));
+    TRY(stage_out(ctx, sums, c.sums, 2 * (size_t)S));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (long s = 0; s < 2 * S; ++s)
+        if (!std::isfinite(sums[s])) return PGPS_E_NUMERIC;
+    return PGPS_OK;
 }

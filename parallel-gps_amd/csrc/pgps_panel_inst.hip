@@ -5,8 +5,8 @@
 // launch_gp_panel lays a call out.  Series run in GROUPS: a group is one launch's grid.y (at most 65535 series) and holds as
 // many consecutive series as fit the context's batch budget (pgps_set_batch_scratch; one series is the least a group can
 // hold).  Everything a group needs besides the caller's arrays is carved from the context's scratch and reused by the next
-// group on the same stream: the merged slots, the filtered moments, the scan records (ctx->ws), the kept states and the
-// gradient partials (ctx->gadj).  A series' record does not depend on the group it lands in except through WHERE its slices
+// group on the same stream: the merged slots, the filtered moments (of the merged series; in the predictive checks, PANEL_LOO,
+// of every series: no merge, no kept states), the scan records (ctx->ws), the kept states and the gradient partials (ctx->gadj).  A series' record does not depend on the group it lands in except through WHERE its slices
 // lie, and no arithmetic does: results do not depend on the grouping.
 #include <cstring>
 #include <vector>
@@ -56,13 +56,13 @@ struct PanelTotals {
 
 template <int D>
 struct PanelParts {
-    Part<double> ts_m, ys_m, rs_m, fms, fPs, spine, lpre, sspine, lsuf, ll;
+    Part<double> ts_m, ys_m, rs_m, fms, fPs, spine, lpre, sspine, lsuf, ll, lpd;
     Part<int> qslot;
     Part<double> xs, gpart;     // (in the second carver)
 };
 
 template <int D>
-static PanelParts<D> panel_lay(Carver& cw, Carver& cg, const PanelTotals& t, bool het) {
+static PanelParts<D> panel_lay(Carver& cw, Carver& cg, const PanelTotals& t, bool het, bool loo) {
     constexpr int NST = gp_adj_nstat<D>();
     PanelParts<D> p;
     p.ts_m = cw.part<double>(t.merged); p.ys_m = cw.part<double>(t.merged); p.rs_m = cw.part<double>(het ? t.merged : 0);
@@ -71,6 +71,7 @@ static PanelParts<D> panel_lay(Carver& cw, Carver& cg, const PanelTotals& t, boo
     p.spine = cw.part<double>(t.series * Dim<D>::NFILT);  p.lpre = cw.part<double>(t.series * kBlock * Dim<D>::NFILT);
     p.sspine = cw.part<double>(t.series * Dim<D>::NSMTH); p.lsuf = cw.part<double>(t.series * kBlock * Dim<D>::NSMTH);
     p.ll = cw.part<double>(t.series);
+    p.lpd = cw.part<double>(loo ? t.series : 0);        // (the predictive checks' second partial; nothing elsewhere)
     p.xs = cg.part<double>(t.xs);       p.gpart = cg.part<double>(t.series * NST);
     return p;
 }
@@ -79,7 +80,7 @@ template <int D>
 int launch_gp_panel(pgps_ctx* ctx, const PanelCall& c, PanelWhat what) {
     constexpr int NX = D + Dim<D>::SYM, NST = gp_adj_nstat<D>();
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const bool het = c.rs != nullptr, predict = what == PANEL_PREDICT, grad = what == PANEL_GRAD;
+    const bool het = c.rs != nullptr, predict = what == PANEL_PREDICT, grad = what == PANEL_GRAD, loo = what == PANEL_LOO;
     const size_t S = (size_t)c.S, budget = batch_budget_fused(ctx);
     // the records, and the groups they fall into: a record is closed into the current group unless the group's layout would
     // then exceed the budget (or the grid)
@@ -89,7 +90,7 @@ int launch_gp_panel(pgps_ctx* ctx, const PanelCall& c, PanelWhat what) {
     size_t need_w = 0, need_g = 0;
     auto bytes_of = [&](const PanelTotals& t, size_t* w, size_t* g) {
         Carver cw(256), cg(256);
-        panel_lay<D>(cw, cg, t, het);
+        panel_lay<D>(cw, cg, t, het, loo);
         *w = cw.bytes(); *g = cg.bytes();
     };
     for (size_t s = 0; s < S; ++s) {
@@ -104,7 +105,9 @@ int launch_gp_panel(pgps_ctx* ctx, const PanelCall& c, PanelWhat what) {
         r.Lc = (ctx->chunk > 0 && (long)ctx->chunk * kBlock >= (long)r.m) ? ctx->chunk : (own < 1 ? 1 : own);
         r.model = c.nmodels == 1 ? 0 : (int)s;
         const size_t merged = r.k > 0 ? panel_pad((size_t)r.m) : 0;
-        const size_t fm = r.k > 0 ? panel_pad((size_t)r.m * D) : 0, fP = r.k > 0 ? panel_pad((size_t)r.m * D * D) : 0;
+        // the filtered moments the smoother reads back: of the merged series, and in the predictive checks of EVERY series
+        const bool smooth = r.k > 0 || loo;
+        const size_t fm = smooth ? panel_pad((size_t)r.m * D) : 0, fP = smooth ? panel_pad((size_t)r.m * D * D) : 0;
         const size_t xs = grad ? panel_pad((size_t)r.Lc * NX * kBlock) : 0;
         bool open = !groups.empty() && groups.back().t.series < kGridYMax;
         if (open) {
@@ -140,7 +143,7 @@ int launch_gp_panel(pgps_ctx* ctx, const PanelCall& c, PanelWhat what) {
     const dim3 block(kBlock);
     for (const Group& G : groups) {
         Carver cw(256), cg(256);
-        const PanelParts<D> q = panel_lay<D>(cw, cg, G.t, het);
+        const PanelParts<D> q = panel_lay<D>(cw, cg, G.t, het, loo);
         const Scratch s{(char*)ctx->ws.p}, sg{(char*)ctx->gadj.p};         // (ensured above for the largest group)
         PanelArgs p{};
         p.desc = ddesc + G.first;
@@ -158,7 +161,14 @@ int launch_gp_panel(pgps_ctx* ctx, const PanelCall& c, PanelWhat what) {
         const dim3 grid(1, n);
         if (predict && G.queries)
             if (int rc = launch_panel_merge(ctx, p, (unsigned)((G.longest + kMergeTile - 1) / kMergeTile), n)) return rc;
-        if (grad) {
+        if (loo) {
+            PanelLooArgs l{};
+            l.p = p;
+            l.o = GpLooOut<double>{c.osa_mean, c.osa_var, c.loo_mean, c.loo_var, s(q.lpd)};
+            l.sums = c.sums + G.first * 2;
+            if (het) timed_launch(ctx, PGPS_K_FILTER_APPLY, k_gpp_loo<D, true>, grid, block, 0, l);
+            else timed_launch(ctx, PGPS_K_FILTER_APPLY, k_gpp_loo<D, false>, grid, block, 0, l);
+        } else if (grad) {
             if (het) timed_launch(ctx, PGPS_K_FILTER_APPLY, k_gpp_gone<D, true>, grid, block, 0, p);
             else timed_launch(ctx, PGPS_K_FILTER_APPLY, k_gpp_gone<D, false>, grid, block, 0, p);
         } else if (predict) {

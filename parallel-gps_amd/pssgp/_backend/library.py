@@ -97,6 +97,7 @@ _SIGNATURES = (
     # S series at once, each on its own clock
     ("pgps_gp_panel_ll{dev}_f64 pgps_gp_panel_ll_grad{dev}_f64", "PLPIIPPPPP"),
     ("pgps_gp_panel_predict{dev}_f64", "PLPPIIPPPPPPPP"),
+    ("pgps_gp_panel_loo{dev}_f64", "PLPIIPPPPPPPPP"),
     ("pgps_gp_panel_laplace{dev}_f64", "PLPIIPIIPPPDIPPPPP"),
     ("pgps_gp_panel_laplace_grad{dev}_f64", "PLPIIPIIPPPPPPPP"),
     # a series kept on the device

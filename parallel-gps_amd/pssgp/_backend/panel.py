@@ -89,6 +89,7 @@ class PanelData:
         self.ctx = _panel_context(device)
         self.offs, ts_a, ys_a, rs_a = _inputs(offs, ts, ys, rs)
         self.S = self.offs.shape[0] - 1
+        self.ys_host = ys_a             # (gp_panel_loo_dev forms the log densities from it)
         self._bufs = {}
         self._fixed = []
         try:
@@ -169,6 +170,62 @@ def gp_panel_predict_dev(data, models, qoffs, tq):
                       data.rs, dtq, dres, dres + 8 * K, dres + 16 * K)
         data.ctx.d2h(res, dres)
     return res[:K], res[K:2 * K], res[2 * K:]
+
+
+# -- predictive checks of every series (pgps_gp_panel_loo_*) ---------------------------------------------
+_CHECK_ARRAYS = ("osa_mean", "osa_var", "loo_mean", "loo_var")
+
+
+def _checks_result(want, arrays, sums, ys):
+    """The dict of fused.gp_loo over the concatenated rows: the arrays asked for and their log densities (formed here from
+    (ys, mean, var), NaN where ys is: the library stores none), "ll" and "loo_lpd" (S,)."""
+    from .fused import normal_log_density
+    out = {k: v for k, v in arrays.items() if v is not None}
+    for name in ("osa", "loo"):
+        if want[name]:
+            out[f"{name}_log_density"] = normal_log_density(ys, out[f"{name}_mean"], out[f"{name}_var"])
+    out["ll"], out["loo_lpd"] = sums[:, 0].copy(), sums[:, 1].copy()
+    return out
+
+
+def gp_panel_loo(models, offs, ts, ys, rs=None, osa=True, loo=True, device=0):
+    """The predictive checks of every series of a panel in one launch per group (pgps_gp_panel_loo_f64), host arrays: the dict
+    of gp_loo with arrays over the concatenated rows (offs[S],) and "ll", "loo_lpd" of shape (S,).  Series s is what gp_loo
+    returns on series s alone, with the step's noise variance R + rs[k] where rs is given.  osa = loo = False: no per-row
+    array is stored or copied back."""
+    o, ts_a, ys_a, rs_a = _inputs(offs, ts, ys, rs)
+    S = o.shape[0] - 1
+    table, d, nm = _table(models, S)
+    n = int(o[-1])
+    want = {"osa": bool(osa), "loo": bool(loo)}
+    arrays = {k: (np.empty(n, np.float64) if want[k[:3]] else None) for k in _CHECK_ARRAYS}
+    sums = np.zeros((S, 2), np.float64)
+    ctx = _require(get_context(device), "pgps_gp_panel_loo_f64", "pgps_gp_panel_loo_*")
+    ctx.call("pgps_gp_panel_loo_f64", S, _ptr(o), d, nm, _ptr(table), _ptr(ts_a), _ptr(ys_a), _ptr(rs_a),
+             *(_ptr(arrays[k]) for k in _CHECK_ARRAYS), _ptr(sums))
+    return _checks_result(want, arrays, sums, ys_a)
+
+
+def gp_panel_loo_dev(data, models, osa=True, loo=True):
+    """gp_panel_loo on the resident series of `data` (pgps_gp_panel_loo_dev_f64): [sums | the arrays asked for] come back in
+    one copy (none asked for: 2 S doubles); the log densities are formed from the host copy of ys that `data` keeps."""
+    _require(data.ctx, "pgps_gp_panel_loo_dev_f64", "pgps_gp_panel_loo_*")
+    table, d, nm = _table(models, data.S)
+    n = int(data.offs[-1])
+    want = {"osa": bool(osa), "loo": bool(loo)}
+    names = [k for k in _CHECK_ARRAYS if want[k[:3]]]
+    res = np.empty(2 * data.S + len(names) * n, np.float64)
+    with data.ctx.lock:
+        dres = data._buffer("checks", res.nbytes)
+        ptrs = {k: dres + 8 * (2 * data.S + i * n) for i, k in enumerate(names)}
+        data.ctx.call("pgps_gp_panel_loo_dev_f64", data.S, _ptr(data.offs), d, nm, _ptr(table), data.ts, data.ys, data.rs,
+                      *(ptrs.get(k) for k in _CHECK_ARRAYS), dres)
+        data.ctx.d2h(res, dres)
+    sums = res[:2 * data.S].reshape(data.S, 2)
+    arrays = {k: None for k in _CHECK_ARRAYS}
+    for i, k in enumerate(names):
+        arrays[k] = res[2 * data.S + i * n:2 * data.S + (i + 1) * n]
+    return _checks_result(want, arrays, sums, data.ys_host)
 
 
 # -- Laplace inference on a panel (pgps_gp_panel_laplace_*; DESIGN.md section 4ab) ---------------------------------------------

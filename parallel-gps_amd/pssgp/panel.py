@@ -7,6 +7,8 @@ single Matern kernel, float64 -- evaluates all series in ONE call of the panel e
 series) on concatenated arrays that live on the device from construction, or from the assignment of
 `data`, until the panel is dropped.  A series above _backend.PANEL_MAX_STEPS steps (counted merged with its queries in
 predict_f) leaves the panel call: its own internal StateSpaceGP evaluates it and the result is spliced back in place.
+The predictive checks of every series (one_step_ahead, leave_one_out, loo_log_predictive_densities)
+follow the same two routes.
 """
 import numpy as np
 
@@ -67,7 +69,7 @@ class StateSpaceGPPanel:
             obs = list(obs)
             if len(obs) != len(series):
                 raise ValueError(f"observation_variances has {len(obs)} entries, the panel {len(series)} series")
-        data, models = [], []
+        data, models, orders = [], [], []
         for s, pair in enumerate(series):
             if len(pair) != 2:
                 raise ValueError(f"series {s}: expected a pair (t, y)")
@@ -88,8 +90,13 @@ class StateSpaceGPPanel:
             models.append(StateSpaceGP((np.ascontiguousarray(t)[:, None], np.ascontiguousarray(y)[:, None]), self.kernel,
                                        self.noise_variance, parallel=self.parallel, observation_variances=v))
             data.append((pair[0], pair[1]))
+            orders.append(order)
         self._release()
         self._data, self._obs_in, self._models = data, obs, models
+        self._orders = orders           # (the stable sort of every series that was not in time order, else None)
+        # the smallest given variance at an observed row of every series (the predictive checks' rule on the device route)
+        self._obs_floor = None if obs is None else [
+            float(np.min(m.observation_variances[~np.isnan(m.data[1].reshape(-1))], initial=np.inf)) for m in models]
         self.num_series = len(models)
         self._short = [s for s, m in enumerate(models) if m.data[0].shape[0] <= _backend.PANEL_MAX_STEPS]
         self._long = [s for s, m in enumerate(models) if m.data[0].shape[0] > _backend.PANEL_MAX_STEPS]
@@ -294,3 +301,73 @@ class StateSpaceGPPanel:
                 means[s], vars_[s] = mean, var
         return [(np.asarray(means[s])[uniq[s][1].reshape(-1)][:, None].astype(dtype, copy=False),
                  np.asarray(vars_[s])[uniq[s][1].reshape(-1)][:, None].astype(dtype, copy=False)) for s in range(self.num_series)]
+
+    # -- predictive checks ---------------------------------------------------------
+    def _check_noise(self, thetas):
+        """The single model's rule on the device route, where no single model is asked: noise_variance (+ s_k) > 0 wherever y
+        is observed, for every short series (at its own row of thetas)."""
+        for s in self._short:
+            R = float(self.noise_variance if thetas is None else thetas[s, -1])
+            if self._obs_in is None:
+                if not R > 0.0:
+                    raise ValueError(f"the predictive checks need noise_variance > 0, got {R}")
+            elif not R + self._obs_floor[s] > 0.0:
+                raise ValueError("the predictive checks need noise_variance + observation_variances > 0 wherever y is observed")
+
+    def _checks(self, thetas, osa, loo):
+        """A list of S dicts as StateSpaceGP._checks returns them (fp64, rows in TIME order: the order of the single models'
+        data), on either route: the loop of the single models, or ONE gp_panel_loo_dev call on the resident short series with
+        the long ones spliced back from their own models."""
+        thetas, params = self._check_thetas(thetas)
+        out = [None] * self.num_series
+        with StateSpaceGP._parameters_restored(params):
+            alone = None
+            if self._fused() is not None:
+                alone = self._long
+                if self._short:
+                    self._check_noise(thetas)
+                    pd = self._resident()
+                    res = _backend.panel.gp_panel_loo_dev(pd, self._table(thetas, params), osa=osa, loo=loo)
+                    rows = [k for k, v in res.items() if k not in ("ll", "loo_lpd")]
+                    for i, s in enumerate(self._short):
+                        a, b = int(pd.offs[i]), int(pd.offs[i + 1])
+                        out[s] = {k: res[k][a:b] for k in rows}
+                        out[s]["ll"], out[s]["loo_lpd"] = float(res["ll"][i]), float(res["loo_lpd"][i])
+            for s, v in self._each(thetas, params, lambda s, m: m._checks(osa, loo), alone).items():
+                out[s] = v
+        return out
+
+    def _columns(self, out, name):
+        """The triples of series s = 0 .. S - 1 from _checks' dicts: rows put back in the order they were given."""
+        cols = []
+        for s, o in enumerate(out):
+            order = self._orders[s]
+            if order is not None:
+                o = dict(o)
+                for part in ("mean", "var", "log_density"):
+                    back = np.empty_like(o[f"{name}_{part}"])
+                    back[order] = o[f"{name}_{part}"]
+                    o[f"{name}_{part}"] = back
+            cols.append(StateSpaceGP._columns_of(o, name))
+        return cols
+
+    def one_step_ahead(self, thetas=None):
+        """A list of S triples (mean, var, log_density), each (n_i, 1), in the order the rows of series i were given: what
+        StateSpaceGP.one_step_ahead returns on series i alone (at row i of thetas where given).  log_density is NaN at the NaN
+        rows of y.  Computed in fp64 and rounded to the default float.  noise_variance <= 0 (with observation_variances:
+        noise_variance + s_k <= 0 at an observed row) raises ValueError."""
+        return self._columns(self._checks(thetas, True, False), "osa")
+
+    def leave_one_out(self, thetas=None):
+        """A list of S triples (mean, var, log_density) as one_step_ahead returns them: the law of every y_k given ALL OTHER
+        observations of its series (StateSpaceGP.leave_one_out on series i alone), without a refit."""
+        return self._columns(self._checks(thetas, False, True), "loo")
+
+    def loo_log_predictive_densities(self, thetas=None):
+        """(S,): the leave-one-out cross-validation score of every series, the sum of leave_one_out()'s log densities over its
+        observed rows -- which series the model explains badly.  On the device route no per-row array is stored or copied."""
+        return np.asarray([o["loo_lpd"] for o in self._checks(thetas, False, False)], np.float64).astype(config.default_float())
+
+    def loo_log_predictive_density(self):
+        """The sum of loo_log_predictive_densities() at the shared parameters."""
+        return config.default_float()(np.sum(self.loo_log_predictive_densities()))
