@@ -684,6 +684,28 @@ int pgps_gp_panel_loo_dev_f64(pgps_ctx*, long S, const long* offs, int d, int nm
                               const double* ys, const double* rs, double* osa_mean, double* osa_var, double* loo_mean,
                               double* loo_var, double* sums /* (S, 2) */);
 
+/* ---- mean functions of a panel: the whitened Gram matrix of 1 + p columns of every series -------------
+ * V (offs[S], C) row-major over the concatenated rows, C = 1 + p in 1 .. 8: column 0 is y, columns 1 .. p the basis functions of
+ * the series' trend at its own times.  With K_y = K + diag(R + rs) on the observed rows of series s, record s of out is
+ *   [G (C, C) row-major | logdet | n_obs],  G = V_s^T K_y^-1 V_s,  logdet = log det K_y,  n_obs = observed rows (as a double),
+ * which holds the GLS trend coefficients of that series, their covariance and the profile likelihood (pgps_gp_gram_multi_* for
+ * one series; with C = 1, -(n_obs log 2 pi + logdet + G[0]) / 2 is the row of pgps_gp_panel_ll_*).  A row that is NaN in column 0
+ * is a missing step: the other columns are not read there and the row contributes nothing.  G is symmetric bit for bit.
+ * offs, models, rs, PGPS_PANEL_MAX_STEPS, steps per lane, groups and the host / device conventions are those of pgps_gp_panel_ll_*; a
+ * record's bits depend on that series' rows, its model row, C and the pinned chunk alone.  One launch per group.
+ * Errors (no output is touched): those of pgps_gp_panel_ll_*, C outside 1 .. 8, a null out: PGPS_E_INVALID; d outside 1..3:
+ * PGPS_E_UNSUPPORTED_DIM.  The host form also scans V and rs once: a row that is NaN in some columns only, or rs against its rule
+ * at an observed row: PGPS_E_INVALID (PRECONDITIONS of the _dev form); a non-finite logdet: PGPS_E_NUMERIC.
+ * pgps_gp_panel_residual_dev_f64: ys_out[k] = V[k, 0] - sum_j V[k, 1 + j] betas[s, j] for the rows k of series s, the sum taken
+ * left to right, every product and sum rounded once; NaN in column 0 stays NaN.  betas (S, C - 1) [device] (may be NULL at
+ * C = 1), V and ys_out [device]; ys_out may be the ys of another panel call.  Synchronises the stream once to copy offs in. */
+int pgps_gp_panel_gram_f64(pgps_ctx*, long S, const long* offs, int d, int nmodels, const double* models, int C, const double* ts,
+                           const double* V, const double* rs, double* out /* (S, C C + 2) */);
+int pgps_gp_panel_gram_dev_f64(pgps_ctx*, long S, const long* offs, int d, int nmodels, const double* models, int C,
+                               const double* ts, const double* V, const double* rs, double* out /* (S, C C + 2) */);
+int pgps_gp_panel_residual_dev_f64(pgps_ctx*, long S, const long* offs, int C, const double* V, const double* betas,
+                                   double* ys_out);
+
 /* ---- Laplace inference for non-Gaussian observations (fused path, fp64, d <= 3) -------------------------
  * Observations y_k ~ p(y | f(t_k)) with a log-concave likelihood, `lik` one of PGPS_LIK_* with one parameter `par` (csrc/
  * pgps_lik.h: lp = log p, g = lp', W = -lp'' floored at 1e-10, d3 = lp''').  A SITE formed at f is the Gaussian factor

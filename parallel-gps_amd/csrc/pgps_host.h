@@ -224,6 +224,13 @@ template <typename T>
 int gp_predict_batch_merged(pgps_ctx* ctx, int B, size_t m, long K, int d, const double* models_host, const T* ts_m,
                             const T* ys_m, double t0, const int* qslot, T* mean, T* var, double* ll);
 
+// a panel of series (pgps_panel_api.hip), shared with pgps_panel_gram_api.hip
+// everything a panel call can be refused for before anything is staged (ys: the array whose presence is required)
+int panel_check(pgps_ctx* ctx, long S, const long* offs, const long* qoffs, bool predict, int d, int nmodels, const double* models,
+                const double* ts, const double* ys, bool het);
+// the caller's rows [lam | N1 | N2 | Pinf | H | R] re-packed to the fixed device stride (kGpModelStride)
+void panel_pack_models(int nmodels, int d, const double* models, std::vector<double>& packed);
+
 // moments of the mixture of B Gaussians per query column (pgps_post_api.hip)
 int mix_moments_dev(pgps_ctx* ctx, int B, long K, const double* mean, const double* var, const double* w, double* mean_out,
                     double* var_out);

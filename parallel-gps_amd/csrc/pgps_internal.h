@@ -347,6 +347,7 @@ struct GpWhitenOut {
 };
 constexpr int kGramMax = 16;            // columns of the Gram kernels
 constexpr int kGramSlab = 1024;         // rows of W per workgroup of k_gram_partial
+constexpr int kPanelGramMax = 8;        // columns of the panel's Gram kernel (pgps_panel_gram.hip.h)
 // a.N, a.M, a.m, a.R, a.ys set by the caller (training steps only); logdet, n_obs [device].  w (N, M) [device]: the whitened
 // columns are stored there; w null: they stay in scratch and gram (M, M) [device], M <= kGramMax, is formed from them.
 // Geometry and rounds as launch_gp_multi
@@ -426,6 +427,22 @@ template <int D>
 int launch_gp_panel(pgps_ctx* ctx, const PanelCall& c, PanelWhat what);
 // the segmented merge of one group (the d = 1 unit holds it): grid (tiles, series)
 int launch_panel_merge(pgps_ctx* ctx, const PanelArgs& p, unsigned tiles, unsigned series);
+// The whitened Gram matrix of C columns of every series (pgps_panel_gram.hip.h, pgps_panel_gram_inst.hip).
+// offs / models HOST as in PanelCall, everything else device: V (offs[S], C) row-major, out (S, C C + 2) records
+// [G | logdet | n_obs].  Groups, tables and the one synchronisation as launch_gp_panel.  The caller has checked the arguments
+struct PanelGramCall {
+    long S;
+    const long* offs;
+    int nmodels;
+    const double* models;       // (nmodels, kGpModelStride)
+    int C;
+    const double *ts, *V, *rs;
+    double* out;
+};
+template <int D>
+int launch_gp_panel_gram(pgps_ctx* ctx, const PanelGramCall& c);
+// ys_out[k] = V[k, 0] - sum_j V[k, 1 + j] betas[s, j] over the rows of every series (the d = 1 unit holds it); offs HOST
+int launch_panel_residual(pgps_ctx* ctx, long S, const long* offs, int C, const double* V, const double* betas, double* ys_out);
 
 // predictive checks of a fitted model against its own data on the fused path (pgps_loo_inst.hip; fp64, d <= 3):
 // what the OSA flavour of the Kalman pass and the LOO flavour of the smoother write

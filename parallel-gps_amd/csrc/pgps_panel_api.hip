@@ -7,7 +7,7 @@
 using namespace pgps;
 
 // everything a call can be refused for before anything is staged
-static int panel_check(pgps_ctx* ctx, long S, const long* offs, const long* qoffs, bool predict, int d, int nmodels,
+int pgps::panel_check(pgps_ctx* ctx, long S, const long* offs, const long* qoffs, bool predict, int d, int nmodels,
                        const double* models, const double* ts, const double* ys, bool het) {
     if (!ctx || S < 1 || !offs || !models || !ts || !ys) return PGPS_E_INVALID;
     if (predict && !qoffs) return PGPS_E_INVALID;
@@ -30,7 +30,7 @@ static int panel_check(pgps_ctx* ctx, long S, const long* offs, const long* qoff
 
 // the caller's rows [lam | N1 (d d) | N2 (d d) | Pinf (d d) | H (d) | R] re-packed to the fixed device stride (kGpModelStride), as
 // gp_pack_models of pgps_gp_api.hip does for the batched calls (panel_check has validated them)
-static void panel_pack_models(int nmodels, int d, const double* models, std::vector<double>& packed) {
+void pgps::panel_pack_models(int nmodels, int d, const double* models, std::vector<double>& packed) {
     packed.assign((size_t)nmodels * kGpModelStride, 0.0);
     const int dd = d * d, in_stride = 1 + 3 * dd + d + 1;
     for (int m = 0; m < nmodels; ++m) {

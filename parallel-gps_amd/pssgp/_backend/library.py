@@ -98,6 +98,8 @@ _SIGNATURES = (
     ("pgps_gp_panel_ll{dev}_f64 pgps_gp_panel_ll_grad{dev}_f64", "PLPIIPPPPP"),
     ("pgps_gp_panel_predict{dev}_f64", "PLPPIIPPPPPPPP"),
     ("pgps_gp_panel_loo{dev}_f64", "PLPIIPPPPPPPPP"),
+    ("pgps_gp_panel_gram{dev}_f64", "PLPIIPIPPPP"),
+    ("pgps_gp_panel_residual_dev_f64", "PLPIPPP"),
     ("pgps_gp_panel_laplace{dev}_f64", "PLPIIPIIPPPDIPPPPP"),
     ("pgps_gp_panel_laplace_grad{dev}_f64", "PLPIIPIIPPPPPPPP"),
     # a series kept on the device

@@ -41,6 +41,16 @@ def _inputs(offs, ts, ys, rs):
     return o, ts_a, ys_a, rs_a
 
 
+PANEL_GRAM_COLUMNS_MAX = 8      # kPanelGramMax: columns C = 1 + p of pgps_gp_panel_gram_*
+
+
+def _columns(V, n):
+    V_a = np.ascontiguousarray(V, dtype=np.float64)
+    if V_a.ndim != 2 or V_a.shape[0] != n or V_a.shape[1] < 1:
+        raise ValueError(f"V must be ({n}, C) like the concatenated rows, got shape {V_a.shape}")
+    return V_a
+
+
 def gp_panel_ll(models, offs, ts, ys, rs=None, device=0):
     """Log-likelihoods (S,) of the S series cut out of the concatenated ts, ys (and rs: per-observation noise variances, or None)
     by `offs` (S + 1,); `models`: 1 or S entries as gp_ll_batch takes them, or their table (pgps_gp_panel_ll_f64)."""
@@ -85,19 +95,36 @@ class PanelData:
     it; the *_dev functions below run the device-pointer entry points on them.  Query grids and results travel per call
     through buffers that grow as needed and are owned here too."""
 
-    def __init__(self, offs, ts, ys, rs=None, device=0):
+    def __init__(self, offs, ts, ys, rs=None, device=0, V=None):
         self.ctx = _panel_context(device)
         self.offs, ts_a, ys_a, rs_a = _inputs(offs, ts, ys, rs)
         self.S = self.offs.shape[0] - 1
         self.ys_host = ys_a             # (gp_panel_loo_dev forms the log densities from it)
         self._bufs = {}
         self._fixed = []
+        self.V, self.C = None, 0        # the columns [y, Phi] of a panel with a mean function (gp_panel_gram_dev), resident too
         try:
             self.ts, self.ys = self._upload(ts_a), self._upload(ys_a)
             self.rs = None if rs_a is None else self._upload(rs_a)
+            if V is not None:
+                V_a = _columns(V, int(self.offs[-1]))
+                self.V, self.C = self._upload(V_a), V_a.shape[1]
         except Exception:
             self.close()
             raise
+
+    def residual_view(self):
+        """A PanelData on the same ts / rs (borrowed: this object keeps owning them) whose ys is a buffer of this object that
+        gp_panel_residual_dev fills: what the panel calls run on at given trend coefficients, with no row crossing the bus.
+        It has no host copy of ys (the predictive checks' log densities need one)."""
+        view = object.__new__(PanelData)
+        view.ctx, view.offs, view.S = self.ctx, self.offs, self.S
+        view.ts, view.rs, view.V, view.C = self.ts, self.rs, None, 0
+        view.ys = self._buffer("residual", 8 * int(self.offs[-1]))
+        view.ys_host = None
+        view._bufs, view._fixed = self._bufs, []        # (its per-call buffers are this object's; close() frees nothing of its own)
+        view.close = lambda: None
+        return view
 
     def _upload(self, a):
         p = self.ctx.malloc(a.nbytes)
@@ -170,6 +197,67 @@ def gp_panel_predict_dev(data, models, qoffs, tq):
                       data.rs, dtq, dres, dres + 8 * K, dres + 16 * K)
         data.ctx.d2h(res, dres)
     return res[:K], res[K:2 * K], res[2 * K:]
+
+
+# -- mean functions of a panel (pgps_gp_panel_gram_*, pgps_gp_panel_residual_dev_f64) ---------------------
+def _gram_context(ctx):
+    return _require(ctx, "pgps_gp_panel_gram_f64", "pgps_gp_panel_gram_*")
+
+
+def _split_gram(out, C):
+    """(G (S, C, C), logdet (S,), n_obs (S,) int64) of the records [G | logdet | n_obs]."""
+    S = out.shape[0]
+    return (out[:, :C * C].reshape(S, C, C).copy(), out[:, C * C].copy(), np.rint(out[:, C * C + 1]).astype(np.int64))
+
+
+def gp_panel_gram(models, offs, ts, V, rs=None, device=0):
+    """(G (S, C, C), logdet (S,), n_obs (S,)) of the S series cut out of the concatenated ts, V (offs[S], C) by `offs`: G of
+    series s is V_s^T K_y^-1 V_s with K_y = K + diag(R + rs) on its observed rows (column 0 of V is y, NaN = missing; a row is NaN
+    in all columns or in none), logdet = log |K_y| (pgps_gp_panel_gram_f64; C <= PANEL_GRAM_COLUMNS_MAX)."""
+    o = _offsets(offs)
+    V_a = _columns(V, int(o[-1]))
+    o, ts_a, _, rs_a = _inputs(o, ts, V_a[:, 0], rs)
+    S, C = o.shape[0] - 1, V_a.shape[1]
+    table, d, nm = _table(models, S)
+    out = np.empty((S, C * C + 2), np.float64)
+    _gram_context(get_context(device)).call("pgps_gp_panel_gram_f64", S, _ptr(o), d, nm, _ptr(table), C, _ptr(ts_a), _ptr(V_a),
+                                            _ptr(rs_a), _ptr(out))
+    return _split_gram(out, C)
+
+
+def gp_panel_gram_dev(data, models):
+    """gp_panel_gram on the resident ts, V (and rs) of `data` (pgps_gp_panel_gram_dev_f64): the S records come back in one copy."""
+    if data.V is None:
+        raise ValueError("this PanelData holds no columns V")
+    _gram_context(data.ctx)
+    table, d, nm = _table(models, data.S)
+    C = data.C
+    out = np.empty((data.S, C * C + 2), np.float64)
+    with data.ctx.lock:
+        dout = data._buffer("gram", out.nbytes)
+        data.ctx.call("pgps_gp_panel_gram_dev_f64", data.S, _ptr(data.offs), d, nm, _ptr(table), C, data.ts, data.V, data.rs, dout)
+        data.ctx.d2h(out, dout)
+    return _split_gram(out, C)
+
+
+def gp_panel_residual_dev(data, betas, into):
+    """into.ys[k] = V[k, 0] - sum_j V[k, 1 + j] betas[s, j] over the rows of every series s of `data` (its resident V), on the
+    device (pgps_gp_panel_residual_dev_f64): betas (S, C - 1) go up, nothing comes back.  `into`: a PanelData of the same
+    offsets (data.residual_view(), or `data` itself: its ys is overwritten)."""
+    if data.V is None:
+        raise ValueError("this PanelData holds no columns V")
+    _gram_context(data.ctx)
+    if into.S != data.S or not np.array_equal(into.offs, data.offs):
+        raise ValueError("`into` must hold the offsets of `data`")
+    b = np.ascontiguousarray(betas, dtype=np.float64).reshape(data.S, -1)
+    if b.shape[1] != data.C - 1:
+        raise ValueError(f"betas must be ({data.S}, {data.C - 1}), got {np.shape(betas)}")
+    with data.ctx.lock:
+        db = data._buffer("betas", max(8, b.nbytes))
+        if b.nbytes:
+            data.ctx.h2d(db, b)
+        data.ctx.call("pgps_gp_panel_residual_dev_f64", data.S, _ptr(data.offs), data.C, data.V, db, into.ys)
+    return into
 
 
 # -- predictive checks of every series (pgps_gp_panel_loo_*; DESIGN.md section 4ac) ---------------------------------------------

@@ -15,6 +15,7 @@ import numpy as np
 from . import _backend, config
 from .gradients import mask_wrt
 from .model import StateSpaceGP
+from .panel_trend import PanelTrend
 
 
 def _column(a, what, s):
@@ -26,17 +27,25 @@ def _column(a, what, s):
     return a
 
 
-class StateSpaceGPPanel:
-    """StateSpaceGPPanel(series, kernel, noise_variance=1.0, parallel=True, observation_variances=None).
+class StateSpaceGPPanel(PanelTrend):
+    """StateSpaceGPPanel(series, kernel, noise_variance=1.0, parallel=True, observation_variances=None, mean_function=None).
 
     series: a list of S pairs (t_i, y_i), each (n_i,) or (n_i, 1), n_i >= 1; NaN in y is a missing observation.  Times in any
     order: every series is sorted once (stable) at construction.  observation_variances: None, or a list of S arrays of given
     per-observation noise variances, each validated as StateSpaceGP validates its own.
 
     `thetas` of the methods below is in the order of trainable_parameters(): None = the panel's own parameters shared by all
-    series, or (S, P) = one row per series.  The panel's own parameters are restored on every exit path."""
+    series, or (S, P) = one row per series.  The panel's own parameters are restored on every exit path.
 
-    def __init__(self, series, kernel, noise_variance=1.0, parallel=True, observation_variances=None):
+    mean_function: None, or one basis of pssgp.mean_functions: series i then has the trend Phi_i(t) betas[i] (panel_trend.py;
+    DESIGN.md section 4ad), with or without observation_variances.  betas (S, p) is a settable float64 array, zeros at first;
+    every evaluation below models y_i - Phi_i betas[i] and adds Phi(X) betas[i] to the means it returns.  None is the panel
+    exactly as without the argument."""
+
+    def __init__(self, series, kernel, noise_variance=1.0, parallel=True, observation_variances=None, mean_function=None):
+        self._set_mean_function(mean_function)
+        self._data_version = 0
+        self._residual = None
         self.kernel = kernel
         self.noise_variance = float(noise_variance)
         self.parallel = bool(parallel)
@@ -93,6 +102,10 @@ class StateSpaceGPPanel:
             orders.append(order)
         self._release()
         self._data, self._obs_in, self._models = data, obs, models
+        self._data_version += 1
+        self._trend_models = {}
+        if self._mean_function is not None and getattr(self, "_betas", np.zeros((0, 0))).shape != (len(models), self._num_functions):
+            self._betas = np.zeros((len(models), self._num_functions), np.float64)
         self._orders = orders           # (the stable sort of every series that was not in time order, else None)
         # the smallest given variance at an observed row of every series (the predictive checks' rule on the device route)
         self._obs_floor = None if obs is None else [
@@ -107,6 +120,9 @@ class StateSpaceGPPanel:
         pd, self._panel_data = getattr(self, "_panel_data", None), None
         if pd is not None:
             pd.close()
+        kept, self._residual = getattr(self, "_residual", None), None
+        if kept is not None:
+            kept[1]._release()
 
     def __del__(self):
         try:
@@ -122,7 +138,10 @@ class StateSpaceGPPanel:
             ts = np.concatenate([m.data[0].reshape(-1) for m in ms])
             ys = np.concatenate([m.data[1].reshape(-1) for m in ms])
             rs = None if self._obs_in is None else np.concatenate([m.observation_variances for m in ms])
-            self._panel_data = _backend.PanelData(offs, ts, ys, rs)
+            V = None                # (with a mean function: the columns [y, Phi] of every series beside them)
+            if self._mean_function is not None and 1 + self._num_functions <= _backend.PANEL_GRAM_COLUMNS_MAX:
+                V = np.concatenate([self._design_columns(s) for s in self._short])
+            self._panel_data = _backend.PanelData(offs, ts, ys, rs, V=V)
         return self._panel_data
 
     # -- the kernel's forms and parameters --------------------------------------------------------------------
@@ -192,6 +211,8 @@ class StateSpaceGPPanel:
     # -- evaluations -----------------------------------------------------------------------------------------
     def log_likelihoods(self, thetas=None):
         """(S,): the marginal log-likelihood of every series."""
+        if self._mean_function is not None:
+            return self._residual_panel().log_likelihoods(thetas)
         thetas, params = self._check_thetas(thetas)
         dtype = config.default_float()
         out = np.empty(self.num_series, dtype)
@@ -220,6 +241,8 @@ class StateSpaceGPPanel:
     def log_likelihoods_and_grads(self, thetas=None):
         """((S,), (S, P)): every series' log-likelihood and its gradient with respect to trainable_parameters() (at row s of
         thetas where given).  Where the single model has no gradient, its NotImplementedError is raised."""
+        if self._mean_function is not None:
+            return self._residual_panel().log_likelihoods_and_grads(thetas)
         thetas, params = self._check_thetas(thetas)
         S, P = self.num_series, len(params)
         lls, grads = np.empty(S, np.float64), np.empty((S, P), np.float64)
@@ -246,6 +269,8 @@ class StateSpaceGPPanel:
     def log_likelihood_and_grad(self, wrt=None):
         """(sum of the log-likelihoods, its gradient) at the shared parameters.  On the device route the S adjoint rows are
         summed first and contracted once."""
+        if self._mean_function is not None:
+            return self._residual_panel().log_likelihood_and_grad(wrt)
         params = self.trainable_parameters()
         fused = self._fused()
         if fused is None:
@@ -267,6 +292,8 @@ class StateSpaceGPPanel:
     def predict_f(self, Xnews, thetas=None):
         """A list of S pairs (mean (K_i, 1), var (K_i, 1)): the posterior of f at Xnews[i] for series i.  Queries in any order,
         repeated times allowed; an empty Xnews[i] gives empty arrays."""
+        if self._mean_function is not None:
+            return self._trend_predict_f(Xnews, thetas)
         Xnews = list(Xnews)
         if len(Xnews) != self.num_series:
             raise ValueError(f"Xnews has {len(Xnews)} entries, the panel {self.num_series} series")
@@ -356,16 +383,22 @@ class StateSpaceGPPanel:
         StateSpaceGP.one_step_ahead returns on series i alone (at row i of thetas where given).  log_density is NaN at the NaN
         rows of y.  Computed in fp64 and rounded to the default float.  noise_variance <= 0 (with observation_variances:
         noise_variance + s_k <= 0 at an observed row) raises ValueError."""
+        if self._mean_function is not None:
+            return self._trend_check("one_step_ahead", thetas)
         return self._columns(self._checks(thetas, True, False), "osa")
 
     def leave_one_out(self, thetas=None):
         """A list of S triples (mean, var, log_density) as one_step_ahead returns them: the law of every y_k given ALL OTHER
         observations of its series (StateSpaceGP.leave_one_out on series i alone), without a refit."""
+        if self._mean_function is not None:
+            return self._trend_check("leave_one_out", thetas)
         return self._columns(self._checks(thetas, False, True), "loo")
 
     def loo_log_predictive_densities(self, thetas=None):
         """(S,): the leave-one-out cross-validation score of every series, the sum of leave_one_out()'s log densities over its
         observed rows -- which series the model explains badly.  On the device route no per-row array is stored or copied."""
+        if self._mean_function is not None:
+            return self._residual_panel().loo_log_predictive_densities(thetas)
         return np.asarray([o["loo_lpd"] for o in self._checks(thetas, False, False)], np.float64).astype(config.default_float())
 
     def loo_log_predictive_density(self):
