@@ -706,6 +706,44 @@ int pgps_gp_panel_gram_dev_f64(pgps_ctx*, long S, const long* offs, int d, int n
 int pgps_gp_panel_residual_dev_f64(pgps_ctx*, long S, const long* offs, int C, const double* V, const double* betas,
                                    double* ys_out);
 
+/* ---- the panel's GLS solves on the device, and the profile gradient of every series in one call --------
+ * pgps_gp_panel_trend_solve_*: records (S, C C + 2) as pgps_gp_panel_gram_* writes them, C = 1 + p in 1 .. 8.  With g_yy = G[0,0],
+ * b = G[1:,0], A = G[1:,1:] of series s, one lane solves A beta = b by a Cholesky factor of the unit-diagonal scaling of A
+ * (s_i = 1 / sqrt(A_ii), Au = diag(s) A diag(s) = L L^T in a fixed order, every product and sum rounded once):
+ *   betas (S, p)       beta_hat = s o L^-T L^-1 (s o b): exactly what pgps_gp_panel_residual_dev_f64 takes
+ *   sol (S, p p + 4)   [cov (p, p) row-major | profile | flat | logdet_A | status]
+ *                      cov = s o (L^-T L^-1) o s, symmetric bit for bit;  logdet_A = 2 sum log L_ii - 2 sum log s_i;
+ *                      profile = -(n_obs log 2 pi + logdet + g_yy - b . beta_hat) / 2;  flat = profile - logdet_A / 2 + p log 2 pi / 2
+ *   status (a double)  0 solved; 1 an entry of A is not finite or a diagonal entry is <= 0; 2 a pivot's square is <= 0 or not
+ *                      finite; 3 the smallest pivot squared is <= 64 p eps (A is rank deficient to working precision).
+ *                      At status != 0 that series' betas, cov, profile, flat and logdet_A are NaN; no other series is touched.
+ * At C = 1 nothing is solved: status 0, flat = profile = -(n_obs log 2 pi + logdet + g_yy) / 2, logdet_A = 0, betas is not
+ * written and may be NULL.  A series' outputs depend on its own record and C alone.  One launch.  The _dev form (records, betas,
+ * sol device) queues the launch and does not synchronise; the host form returns through vectors of the call.
+ * Errors (no output is touched): S < 1, C outside 1 .. 8, null records or sol, null betas with C > 1: PGPS_E_INVALID.  A
+ * rank-deficient series is data, not an error: PGPS_OK and its status says so.
+ *
+ * pgps_gp_panel_profile_grad_*: for every series the Gram record of V (pgps_gp_panel_gram_*), its solve (above), the residuals
+ * y - Phi beta_hat into ys_work (pgps_gp_panel_residual_dev_f64) and the adjoint pass on them (pgps_gp_panel_ll_grad_*):
+ *   betas (S, C - 1), sol (S, (C-1)^2 + 4) as above;  out (S, 2 + d d + 2 d): row s = [profile ll | Abar | Ubar | Hbar | Rbar],
+ * the record of pgps_gp_panel_ll_grad_* on the residual series (out[s, 0] and sol's profile are one quantity by two routes).  By
+ * definition the bits are those of the four separate _dev calls: the same kernels, steps per lane and grouping rule.  All tables
+ * of both phases ([models | Gram records | adjoint records | offs]) go up in ONE copy behind ONE stream synchronisation before
+ * the first launch; the _dev form (ts .. out device, ys_work (offs[S]) device) then queues every launch and does not synchronise
+ * again.  The host form stages as pgps_gp_panel_gram_f64 does (same scans of V and rs) and returns through vectors of the call.
+ * Errors (no output is touched): those of pgps_gp_panel_gram_*; null sol, out or ys_work, null betas with C > 1: PGPS_E_INVALID.
+ * The host form returns PGPS_E_NUMERIC (outputs written) when a series of status 0 has a non-finite profile or out[s, 0]; a series
+ * whose status != 0 has NaN rows of betas, sol and out, and the call returns PGPS_OK. */
+int pgps_gp_panel_trend_solve_f64(pgps_ctx*, long S, int C, const double* records /* (S, C C + 2) */, double* betas /* (S, C-1) */,
+                                  double* sol /* (S, (C-1)^2 + 4) */);
+int pgps_gp_panel_trend_solve_dev_f64(pgps_ctx*, long S, int C, const double* records, double* betas, double* sol);
+int pgps_gp_panel_profile_grad_f64(pgps_ctx*, long S, const long* offs, int d, int nmodels, const double* models, int C,
+                                   const double* ts, const double* V, const double* rs, double* betas, double* sol,
+                                   double* out /* (S, 2 + d d + 2 d) */);
+int pgps_gp_panel_profile_grad_dev_f64(pgps_ctx*, long S, const long* offs, int d, int nmodels, const double* models, int C,
+                                       const double* ts, const double* V, const double* rs, double* betas, double* sol,
+                                       double* ys_work /* (offs[S]) */, double* out /* (S, 2 + d d + 2 d) */);
+
 /* ---- Laplace inference for non-Gaussian observations (fused path, fp64, d <= 3) -------------------------
  * Observations y_k ~ p(y | f(t_k)) with a log-concave likelihood, `lik` one of PGPS_LIK_* with one parameter `par` (csrc/
  * pgps_lik.h: lp = log p, g = lp', W = -lp'' floored at 1e-10, d3 = lp''').  A SITE formed at f is the Gaussian factor

@@ -230,6 +230,13 @@ int panel_check(pgps_ctx* ctx, long S, const long* offs, const long* qoffs, bool
                 const double* ts, const double* ys, bool het);
 // the caller's rows [lam | N1 | N2 | Pinf | H | R] re-packed to the fixed device stride (kGpModelStride)
 void panel_pack_models(int nmodels, int d, const double* models, std::vector<double>& packed);
+// the Gram calls' checks (pgps_panel_gram_api.hip), shared with pgps_panel_trend_api.hip: panel_check on V, C in 1 .. kPanelGramMax
+// and a non-null out; and the host forms' one pass over V (a row is NaN in all columns or in none) and rs (the rule of
+// pgps_gp_panel_ll_f64 at the observed rows)
+int panel_gram_check(pgps_ctx* ctx, long S, const long* offs, int d, int nmodels, const double* models, int C, const double* ts,
+                     const double* V, bool het, const double* out);
+bool panel_gram_rows_valid(long S, const long* offs, int d, int nmodels, const double* models, int C, const double* V,
+                           const double* rs);
 
 // moments of the mixture of B Gaussians per query column (pgps_post_api.hip)
 int mix_moments_dev(pgps_ctx* ctx, int B, long K, const double* mean, const double* var, const double* w, double* mean_out,

@@ -7,8 +7,8 @@
 
 using namespace pgps;
 
-static int gram_check(pgps_ctx* ctx, long S, const long* offs, int d, int nmodels, const double* models, int C, const double* ts,
-                      const double* V, bool het, const double* out) {
+int pgps::panel_gram_check(pgps_ctx* ctx, long S, const long* offs, int d, int nmodels, const double* models, int C, const double* ts,
+                           const double* V, bool het, const double* out) {
     TRY(panel_check(ctx, S, offs, nullptr, false, d, nmodels, models, ts, V, het));
     if (C < 1 || C > kPanelGramMax || !out) return PGPS_E_INVALID;
     return PGPS_OK;
@@ -16,8 +16,8 @@ static int gram_check(pgps_ctx* ctx, long S, const long* offs, int d, int nmodel
 
 // the host form's one pass over V and rs: a row is observed in all columns or in none (the rule of pgps_gp_*_multi_f64), and
 // at the observed rows rs is finite, >= 0 and R + rs[k] > 0 (the rule of pgps_gp_panel_ll_f64)
-static bool gram_rows_valid(long S, const long* offs, int d, int nmodels, const double* models, int C, const double* V,
-                            const double* rs) {
+bool pgps::panel_gram_rows_valid(long S, const long* offs, int d, int nmodels, const double* models, int C, const double* V,
+                                 const double* rs) {
     const int in_stride = 1 + 3 * d * d + d + 1;
     for (long s = 0; s < S; ++s) {
         const double R = models[(size_t)(nmodels == 1 ? 0 : s) * in_stride + in_stride - 1];
@@ -41,7 +41,7 @@ static int gram_dev(pgps_ctx* ctx, int d, const PanelGramCall& c) {
 
 extern "C" int pgps_gp_panel_gram_dev_f64(pgps_ctx* ctx, long S, const long* offs, int d, int nmodels, const double* models, int C,
                                           const double* ts, const double* V, const double* rs, double* out) {
-    TRY(gram_check(ctx, S, offs, d, nmodels, models, C, ts, V, rs != nullptr, out));
+    TRY(panel_gram_check(ctx, S, offs, d, nmodels, models, C, ts, V, rs != nullptr, out));
     std::vector<double> packed;
     panel_pack_models(nmodels, d, models, packed);
     PanelGramCall c{};
@@ -51,8 +51,8 @@ extern "C" int pgps_gp_panel_gram_dev_f64(pgps_ctx* ctx, long S, const long* off
 
 extern "C" int pgps_gp_panel_gram_f64(pgps_ctx* ctx, long S, const long* offs, int d, int nmodels, const double* models, int C,
                                       const double* ts, const double* V, const double* rs, double* out) {
-    TRY(gram_check(ctx, S, offs, d, nmodels, models, C, ts, V, rs != nullptr, out));
-    if (!gram_rows_valid(S, offs, d, nmodels, models, C, V, rs)) return PGPS_E_INVALID;
+    TRY(panel_gram_check(ctx, S, offs, d, nmodels, models, C, ts, V, rs != nullptr, out));
+    if (!panel_gram_rows_valid(S, offs, d, nmodels, models, C, V, rs)) return PGPS_E_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t N = (size_t)offs[S], rec = (size_t)C * C + 2;
     std::vector<double> packed;

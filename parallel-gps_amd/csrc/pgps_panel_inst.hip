@@ -13,6 +13,7 @@
 
 #include "pgps_merge.hip.h"
 #include "pgps_panel.hip.h"
+#include "pgps_panel_plan.h"
 #include "pgps_scratch.h"
 
 #ifndef PGPS_PANEL_D
@@ -49,11 +50,6 @@ int launch_panel_merge(pgps_ctx* ctx, const PanelArgs& p, unsigned tiles, unsign
 
 static inline size_t panel_pad(size_t n) { return align_up(n, (size_t)kPanelAlign); }
 
-// what a group of series needs: counts of elements, every ragged slice padded to kPanelAlign
-struct PanelTotals {
-    size_t series = 0, merged = 0, fm = 0, fP = 0, xs = 0;
-};
-
 template <int D>
 struct PanelParts {
     Part<double> ts_m, ys_m, rs_m, fms, fPs, spine, lpre, sspine, lsuf, ll, lpd;
@@ -76,17 +72,17 @@ static PanelParts<D> panel_lay(Carver& cw, Carver& cg, const PanelTotals& t, boo
     return p;
 }
 
+// the records, and the groups they fall into: a record is closed into the current group unless the group's layout would then
+// exceed the budget (or the grid)
 template <int D>
-int launch_gp_panel(pgps_ctx* ctx, const PanelCall& c, PanelWhat what) {
-    constexpr int NX = D + Dim<D>::SYM, NST = gp_adj_nstat<D>();
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+void panel_plan(const pgps_ctx* ctx, const PanelCall& c, PanelWhat what, PanelPlan& plan) {
+    constexpr int NX = D + Dim<D>::SYM;
     const bool het = c.rs != nullptr, predict = what == PANEL_PREDICT, grad = what == PANEL_GRAD, loo = what == PANEL_LOO;
     const size_t S = (size_t)c.S, budget = batch_budget_fused(ctx);
-    // the records, and the groups they fall into: a record is closed into the current group unless the group's layout would
-    // then exceed the budget (or the grid)
-    std::vector<PanelDesc> desc(S);
-    struct Group { size_t first; PanelTotals t; int longest = 0; bool queries = false; };
-    std::vector<Group> groups;
+    std::vector<PanelDesc>& desc = plan.desc;
+    std::vector<PanelGroup>& groups = plan.groups;
+    desc.assign(S, PanelDesc{});
+    groups.clear();
     size_t need_w = 0, need_g = 0;
     auto bytes_of = [&](const PanelTotals& t, size_t* w, size_t* g) {
         Carver cw(256), cg(256);
@@ -117,8 +113,8 @@ int launch_gp_panel(pgps_ctx* ctx, const PanelCall& c, PanelWhat what) {
             bytes_of(t, &w, &g);
             open = w + g <= budget;
         }
-        if (!open) groups.push_back(Group{s, PanelTotals{}});
-        Group& G = groups.back();
+        if (!open) groups.push_back(PanelGroup{s, PanelTotals{}});
+        PanelGroup& G = groups.back();
         r.slot = (int)G.t.series;
         r.m0 = (long)G.t.merged; r.o_fm = (long)G.t.fm; r.o_fP = (long)G.t.fP; r.o_xs = (long)G.t.xs;
         G.t.series += 1; G.t.merged += merged; G.t.fm += fm; G.t.fP += fP; G.t.xs += xs;
@@ -128,26 +124,22 @@ int launch_gp_panel(pgps_ctx* ctx, const PanelCall& c, PanelWhat what) {
         if (w > need_w) need_w = w;
         if (g > need_g) need_g = g;
     }
-    // both tables in ONE copy, [models | records], and the one synchronisation of the call: the host vectors die with it
-    const size_t mbytes = align_up((size_t)c.nmodels * kGpModelStride * sizeof(double), 256);
-    std::vector<char> tables(mbytes + S * sizeof(PanelDesc));
-    memcpy(tables.data(), c.models, (size_t)c.nmodels * kGpModelStride * sizeof(double));
-    memcpy(tables.data() + mbytes, desc.data(), S * sizeof(PanelDesc));
-    if (int rc = ensure(ctx, ctx->panel, tables.size())) return rc;
-    if (int rc = ensure(ctx, ctx->ws, need_w)) return rc;
-    if (int rc = ensure(ctx, ctx->gadj, need_g)) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->panel.p, tables.data(), tables.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    const PanelDesc* ddesc = reinterpret_cast<const PanelDesc*>((const char*)ctx->panel.p + mbytes);
+    plan.need_w = need_w; plan.need_g = need_g;
+}
 
+template <int D>
+int panel_enqueue(pgps_ctx* ctx, const PanelCall& c, PanelWhat what, const PanelPlan& plan, const double* dmodels,
+                  const PanelDesc* ddesc) {
+    constexpr int NST = gp_adj_nstat<D>();
+    const bool het = c.rs != nullptr, predict = what == PANEL_PREDICT, grad = what == PANEL_GRAD, loo = what == PANEL_LOO;
     const dim3 block(kBlock);
-    for (const Group& G : groups) {
+    for (const PanelGroup& G : plan.groups) {
         Carver cw(256), cg(256);
         const PanelParts<D> q = panel_lay<D>(cw, cg, G.t, het, loo);
-        const Scratch s{(char*)ctx->ws.p}, sg{(char*)ctx->gadj.p};         // (ensured above for the largest group)
+        const Scratch s{(char*)ctx->ws.p}, sg{(char*)ctx->gadj.p};         // (sized by the caller for the largest group)
         PanelArgs p{};
         p.desc = ddesc + G.first;
-        p.models = reinterpret_cast<const double*>(ctx->panel.p);
+        p.models = dmodels;
         p.ts = c.ts; p.ys = c.ys; p.rs = c.rs; p.tq = c.tq;
         p.ts_m = s(q.ts_m); p.ys_m = s(q.ys_m); p.rs_m = s(q.rs_m); p.qslot = s(q.qslot);
         p.pmean = c.mean; p.pvar = c.var;
@@ -183,6 +175,29 @@ int launch_gp_panel(pgps_ctx* ctx, const PanelCall& c, PanelWhat what) {
     return PGPS_OK;
 }
 
+// plan, both tables in ONE copy, [models | records], and the one synchronisation of the call (the host vectors die with it),
+// then the launches
+template <int D>
+int launch_gp_panel(pgps_ctx* ctx, const PanelCall& c, PanelWhat what) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PanelPlan plan;
+    panel_plan<D>(ctx, c, what, plan);
+    const size_t S = (size_t)c.S;
+    const size_t mbytes = align_up((size_t)c.nmodels * kGpModelStride * sizeof(double), 256);
+    std::vector<char> tables(mbytes + S * sizeof(PanelDesc));
+    memcpy(tables.data(), c.models, (size_t)c.nmodels * kGpModelStride * sizeof(double));
+    memcpy(tables.data() + mbytes, plan.desc.data(), S * sizeof(PanelDesc));
+    if (int rc = ensure(ctx, ctx->panel, tables.size())) return rc;
+    if (int rc = ensure(ctx, ctx->ws, plan.need_w)) return rc;
+    if (int rc = ensure(ctx, ctx->gadj, plan.need_g)) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->panel.p, tables.data(), tables.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return panel_enqueue<D>(ctx, c, what, plan, reinterpret_cast<const double*>(ctx->panel.p),
+                            reinterpret_cast<const PanelDesc*>((const char*)ctx->panel.p + mbytes));
+}
+
+template void panel_plan<PGPS_PANEL_D>(const pgps_ctx*, const PanelCall&, PanelWhat, PanelPlan&);
+template int panel_enqueue<PGPS_PANEL_D>(pgps_ctx*, const PanelCall&, PanelWhat, const PanelPlan&, const double*, const PanelDesc*);
 template int launch_gp_panel<PGPS_PANEL_D>(pgps_ctx*, const PanelCall&, PanelWhat);
 
 }  // namespace pgps

@@ -21,6 +21,7 @@ from .batch import (_gp_rows, _lti_table, gp_ll_batch, gp_ll_grad_adj_batch, gp_
 from .series import PackBuffer, Series, _Packed
 from . import panel
 from .panel import (NEWTON_MAX_ITER_CAP, PANEL_GRAM_COLUMNS_MAX, PANEL_INFO, PANEL_MAX_STEPS, PanelData, gp_panel_gram,
-                    gp_panel_laplace, gp_panel_laplace_grad, gp_panel_ll, gp_panel_ll_grad, gp_panel_loo, gp_panel_predict)
+                    gp_panel_laplace, gp_panel_laplace_grad, gp_panel_ll, gp_panel_ll_grad, gp_panel_loo, gp_panel_predict,
+                    gp_panel_trend_solve)
 from .sites import (LIK_BERNOULLI_LOGIT, LIK_GAUSSIAN, LIK_POISSON_EXP, LIK_W_MIN, NEWTON_SUMS, SiteBuffers, gp_newton,
                     lik_sites)

@@ -100,6 +100,9 @@ _SIGNATURES = (
     ("pgps_gp_panel_loo{dev}_f64", "PLPIIPPPPPPPPP"),
     ("pgps_gp_panel_gram{dev}_f64", "PLPIIPIPPPP"),
     ("pgps_gp_panel_residual_dev_f64", "PLPIPPP"),
+    ("pgps_gp_panel_trend_solve{dev}_f64", "PLIPPP"),
+    ("pgps_gp_panel_profile_grad_f64", "PLPIIPIPPPPPP"),
+    ("pgps_gp_panel_profile_grad_dev_f64", "PLPIIPIPPPPPPP"),
     ("pgps_gp_panel_laplace{dev}_f64", "PLPIIPIIPPPDIPPPPP"),
     ("pgps_gp_panel_laplace_grad{dev}_f64", "PLPIIPIIPPPPPPPP"),
     # a series kept on the device

@@ -260,6 +260,61 @@ def gp_panel_residual_dev(data, betas, into):
     return into
 
 
+# -- the GLS solves on the device and the profile gradient in one call (pgps_gp_panel_trend_solve_*, pgps_gp_panel_profile_grad_*;
+#    DESIGN.md section 4ae) -----------------------------------------------------------------------------------------------------
+SOL_FIELDS = ("profile", "flat", "logdet_A", "status")     # what follows cov (p, p) in a row of sol
+
+
+def _trend_context(ctx):
+    return _require(ctx, "pgps_gp_panel_profile_grad_dev_f64", "pgps_gp_panel_profile_grad_*")
+
+
+def split_sol(sol, p):
+    """A dict of the rows of sol (S, p p + 4): "cov" (S, p, p), "profile", "flat", "logdet_A" (S,), "status" (S,) int64."""
+    S = sol.shape[0]
+    out = {"cov": sol[:, :p * p].reshape(S, p, p).copy()}
+    for i, name in enumerate(SOL_FIELDS):
+        out[name] = sol[:, p * p + i].copy()
+    out["status"] = np.rint(out["status"]).astype(np.int64)
+    return out
+
+
+def gp_panel_trend_solve(records, C, device=0):
+    """(betas_hat (S, C - 1), sol (S, (C - 1)^2 + 4)) of the Gram records (S, C C + 2) = [G | logdet | n_obs] as pgps_gp_panel_gram_*
+    writes them: every series' GLS solve by one lane of one launch (pgps_gp_panel_trend_solve_f64).  A row of sol is
+    [cov (p, p) | profile | flat | logdet_A | status] (split_sol); a series whose status is not 0 has NaN rows."""
+    C = int(C)
+    r = np.ascontiguousarray(records, dtype=np.float64)
+    if not 1 <= C <= PANEL_GRAM_COLUMNS_MAX or r.ndim != 2 or r.shape[0] < 1 or r.shape[1] != C * C + 2:
+        raise ValueError(f"records must be (S, C C + 2) with C = {C} in 1 .. {PANEL_GRAM_COLUMNS_MAX}, got shape {r.shape}")
+    S, p = r.shape[0], C - 1
+    betas, sol = np.empty((S, p), np.float64), np.empty((S, p * p + 4), np.float64)
+    _trend_context(get_context(device)).call("pgps_gp_panel_trend_solve_f64", S, C, _ptr(r), _ptr(betas) if p else None, _ptr(sol))
+    return betas, sol
+
+
+def gp_panel_profile_grad_dev(data, models):
+    """(rows (S, 1 + d d + 2 d + 1), betas_hat (S, C - 1), sol (S, (C - 1)^2 + 4)) on the resident ts, V (and rs) of `data`
+    (pgps_gp_panel_profile_grad_dev_f64): Gram, solve, residuals and the adjoint pass queued back to back.  rows[s] is the record of
+    gp_panel_ll_grad_dev on the residual series y_s - Phi_s betas_hat[s], which are left in the buffer of data.residual_view().
+    The three outputs lie in ONE buffer of `data` and come back in ONE copy."""
+    if data.V is None:
+        raise ValueError("this PanelData holds no columns V")
+    _trend_context(data.ctx)
+    table, d, nm = _table(models, data.S)
+    S, C = data.S, data.C
+    p, nout = C - 1, 2 + d * d + 2 * d
+    nb, ns = S * p, S * (p * p + 4)
+    res = np.empty(nb + ns + S * nout, np.float64)              # [betas | sol | rows]
+    with data.ctx.lock:
+        work = data.residual_view().ys
+        dres = data._buffer("profile", res.nbytes)
+        data.ctx.call("pgps_gp_panel_profile_grad_dev_f64", S, _ptr(data.offs), d, nm, _ptr(table), C, data.ts, data.V, data.rs,
+                      dres, dres + 8 * nb, work, dres + 8 * (nb + ns))
+        data.ctx.d2h(res, dres)
+    return res[nb + ns:].reshape(S, nout), res[:nb].reshape(S, p), res[nb:nb + ns].reshape(S, p * p + 4)
+
+
 # -- predictive checks of every series (pgps_gp_panel_loo_*; DESIGN.md section 4ac) ---------------------------------------------
 _CHECK_ARRAYS = ("osa_mean", "osa_var", "loo_mean", "loo_var")
 

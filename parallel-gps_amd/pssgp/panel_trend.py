@@ -8,6 +8,8 @@ forms all short series' Gram matrices in ONE call (_backend.panel.gp_panel_gram_
 live on the device beside the series.  Everything else -- parallel=False, other kernels, float32, more columns, a series above
 _backend.PANEL_MAX_STEPS steps (spliced back) -- is the loop: with scalar noise a StateSpaceGP(..., mean_function=...) on the series,
 with observation_variances (where the single model has no such route) the host twin below.
+profile_log_likelihoods_and_grads goes further on that route: Gram, the S small solves (one lane per series, where the Gram
+records lie), the residuals and the adjoint pass are ONE call (_backend.panel.gp_panel_profile_grad_dev).
 
 The evaluations the panel had before have GPflow's meaning at the CURRENT betas: they run on the residual panel
 (t_i, y_i - Phi_i beta_i), kept until betas or data change; Phi(X) beta_i is added to returned means.
@@ -18,7 +20,7 @@ from . import _backend, config
 from .gradients import mask_wrt
 from .kalman import sequential
 from .model import StateSpaceGP
-from .trend import _LOG_2PI, MeanGram, _chol_design, _chol_solve
+from .trend import _LOG_2PI, RANK_MESSAGES, MeanGram, _chol_design, _chol_solve
 
 
 def whiten_host(kernel, noise_variance, t, V, observation_variances=None):
@@ -55,7 +57,8 @@ def _mean_gram(G, logdet, n_obs):
 
 class PanelTrend:
     """mean_function, betas, mean_grams, mean_coefficients, fit_mean_functions, profile_log_likelihoods,
-    log_marginal_likelihoods_flat_mean, profile_log_likelihood_and_grad, and the residual panel of the delegated evaluations."""
+    log_marginal_likelihoods_flat_mean, profile_log_likelihood_and_grad, profile_log_likelihoods_and_grads, and the residual
+    panel of the delegated evaluations."""
 
     # -- the basis and the coefficients ----------------------------------------------------------------------
     @property
@@ -218,6 +221,86 @@ class PanelTrend:
             l1, g1 = self._single_grad(single)
             ll, g = ll + l1, g + g1
         return np.float64(ll), mask_wrt(g, wrt)
+
+    def _residual_single(self, s, beta):
+        """The zero-mean single model on (t_s, y_s - Phi_s beta) at the panel's current setting."""
+        m = self._models[s]
+        ts, ys = m.data
+        res = (np.asarray(ys, np.float64) - (self._mean_function.design(ts.reshape(-1)) @ beta)[:, None]).astype(ys.dtype)
+        return StateSpaceGP((ts, res), self.kernel, self.noise_variance, parallel=self.parallel,
+                            observation_variances=m.observation_variances)
+
+    def profile_log_likelihoods_and_grads(self, thetas=None, reduce=None):
+        """reduce=None: ((S,), (S, P)) over trainable_parameters() -- row s is the profile log-likelihood of series s at its own
+        beta_hat and its gradient, at row s of thetas where given.  At beta_hat d ll / d beta = 0, so the gradient is that of
+        the plain likelihood of the residuals y_s - Phi_s beta_hat_s.  reduce="sum": (float64, (P,)) at the shared parameters
+        (thetas must be None): the S rows are summed and contracted ONCE, as log_likelihood_and_grad does -- the meaning of
+        profile_log_likelihood_and_grad() without its host solves.
+
+        Device route: ONE _backend.panel.gp_panel_profile_grad_dev call on the short series -- Gram, the S solves, the
+        residuals and the adjoint pass queued back to back on the device -- with the long series spliced back.  Everything
+        else is the loop: all solves first (a rank-deficient series raises ValueError and is named before any gradient is
+        asked for), then the residual model's log_likelihood_and_grad() per series.  betas and the panel's parameters stay as
+        they are, on the error paths too."""
+        self._need_mean()
+        if reduce not in (None, "sum"):
+            raise ValueError(f"reduce must be None or 'sum', got {reduce!r}")
+        if reduce == "sum" and thetas is not None:
+            raise ValueError("reduce='sum' is the population objective at the shared parameters: thetas must be None")
+        thetas, params = self._check_thetas(thetas)
+        S, P = self.num_series, len(params)
+        lls, grads = np.empty(S, np.float64), np.zeros((S, P), np.float64)
+        total_ll, total_g = 0.0, np.zeros(P, np.float64)
+        with StateSpaceGP._parameters_restored(params):
+            alone, failed = range(S), {}
+            if self._trend_on_device():
+                fused = self._fused()
+                rows, _, sol = _backend.panel.gp_panel_profile_grad_dev(self._resident(), self._table(thetas, params))
+                p = self._num_functions
+                status = np.rint(sol[:, p * p + 3]).astype(np.int64)
+                for i in np.flatnonzero(status != 0):
+                    failed[self._short[int(i)]] = RANK_MESSAGES[int(status[i])]
+                d = fused[1][1].shape[0]
+                helper = self._helper()
+                if failed:
+                    pass                    # (raised below, behind the loop's solves: the lowest such series is named)
+                elif reduce == "sum":
+                    total = np.sum(rows, axis=0)
+                    total_ll += float(total[0])
+                    total_g += helper._host_adjoint_grad(fused, _backend.split_grad_stats(total, d), None)
+                else:
+                    for i, s in enumerate(self._short):
+                        if thetas is not None:              # (the contraction reads the kernel's setting: row s)
+                            StateSpaceGP._assign(params, thetas[s])
+                            fused = self._fused()
+                        lls[s] = rows[i, 0]
+                        grads[s] = helper._host_adjoint_grad(fused, _backend.split_grad_stats(rows[i], d), None)
+                alone = self._long
+            alone = list(alone)
+            # the loop: every solve before any gradient
+            betas_hat = {}
+            for s in alone:
+                if thetas is not None:
+                    StateSpaceGP._assign(params, thetas[s])
+                g = self._single_gram(s)
+                try:
+                    L, sc = _chol_design(g.A)
+                except ValueError as e:
+                    failed[s] = str(e)
+                    continue
+                betas_hat[s] = _chol_solve(L, sc, g.b)
+            if failed:                      # (the lowest such series, as _solved names it)
+                s = min(failed)
+                raise ValueError(f"series {s}: {failed[s]}")
+            for s in alone:
+                if thetas is not None:
+                    StateSpaceGP._assign(params, thetas[s])
+                l1, g1 = self._single_grad(self._residual_single(s, betas_hat[s]))
+                lls[s], grads[s] = l1, g1
+                total_ll, total_g = total_ll + l1, total_g + g1
+        if reduce == "sum":
+            return np.float64(total_ll), total_g
+        return lls, grads
 
     # -- GPflow's meaning of the evaluations the panel had before: the GPs model y_i - m_i(t) ---------------
     def _residual_panel(self):

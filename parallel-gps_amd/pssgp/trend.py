@@ -40,6 +40,12 @@ class MeanGram:
     A: np.ndarray
 
 
+_RANK = "the mean function's design matrix does not have full column rank on the observed rows"
+# _chol_design's refusals, under the status the device solve gives them (csrc/pgps_panel_trend.hip.h)
+RANK_MESSAGES = {1: _RANK + " (a basis function is zero or not finite there)", 2: _RANK,
+                 3: _RANK + " (its basis functions are linearly dependent)"}
+
+
 def _chol_design(A):
     """(L, s) with diag(s) A diag(s) = L L^T, s = 1 / sqrt(diag A): the factor of A on unit diagonal, so that a pivot measures
     how much of a basis function its predecessors leave.  ValueError when the design matrix has no full column rank on the
@@ -47,16 +53,15 @@ def _chol_design(A):
     A = np.asarray(A, np.float64)
     p = A.shape[0]
     dg = np.diag(A)
-    bad = "the mean function's design matrix does not have full column rank on the observed rows"
     if not (np.all(np.isfinite(A)) and np.all(dg > 0.0)):
-        raise ValueError(bad + " (a basis function is zero or not finite there)")
+        raise ValueError(RANK_MESSAGES[1])
     s = 1.0 / np.sqrt(dg)
     try:
         L = np.linalg.cholesky(A * s[:, None] * s[None, :])
     except np.linalg.LinAlgError:
-        raise ValueError(bad) from None
+        raise ValueError(RANK_MESSAGES[2]) from None
     if np.min(np.diag(L)) ** 2 <= 64.0 * p * np.finfo(np.float64).eps:
-        raise ValueError(bad + " (its basis functions are linearly dependent)")
+        raise ValueError(RANK_MESSAGES[3])
     return L, s
 
 
