@@ -148,6 +148,11 @@ int pgps_get_geometry(pgps_ctx* ctx, long N, int d, int* lanes, int* steps_per_l
  * 2 or 4 = steps per lane per staged sub-tile (2: fp64 only).  Tuning / A-B knob. */
 int pgps_set_stage(pgps_ctx* ctx, int steps_per_subtile);
 int pgps_get_chunk(pgps_ctx* ctx, long n_steps, int* steps_per_lane, int* n_workgroups);
+/* What the batched fused launches of B models over n_steps steps run with (pgps_gp_ll_batch_*, the three-launch form of
+ * pgps_gp_predict_batch_* -- n_steps = N + K there -- and the four-launch road of pgps_gp_ll_grad_adj_batch_*): steps per
+ * lane -- pgps_set_chunk's value, else 16 while B x workgroups >= 1024, halved towards 4 -- and the 256-lane workgroups per
+ * model by it.  Read-only.  Errors: B < 1, n_steps < 1, a null pointer: PGPS_E_INVALID. */
+int pgps_get_batch_chunk(pgps_ctx* ctx, int B, long n_steps, int* steps_per_lane, int* n_workgroups);
 /* Which kernel family a pkf (what = 0) / pks (1) / pkfs (2) call -- or a phase of the segment protocol (3) -- of n_steps at
  * state dimension d will run on under the context's settings (float32 arithmetic if f32 != 0; a float32 smoother call that
  * is promoted to fp64 arithmetic, pgps_set_f32_policy, takes the fp64 answer): what a benchmark needs to name the kernels it

@@ -525,6 +525,14 @@ extern "C" int pgps_get_chunk(pgps_ctx* ctx, long N, int* Lc, int* nb) {
     geometry(ctx, N, Lc, nb);
     return PGPS_OK;
 }
+// ... and of the batched fused launches: batch_steps_per_lane and the workgroups per model by it (launch_gp_batch, form 2 of
+// launch_gp_predict_batch, the four-launch road of launch_gp_adj_batch: pgps_inst.hip)
+extern "C" int pgps_get_batch_chunk(pgps_ctx* ctx, int B, long N, int* Lc, int* nb) {
+    if (!ctx || B < 1 || N < 1 || !Lc || !nb) return PGPS_E_INVALID;
+    *Lc = batch_steps_per_lane(ctx, B, N);
+    *nb = (int)((N + (long)kBlock * *Lc - 1) / ((long)kBlock * *Lc));
+    return PGPS_OK;
+}
 // ---------------------------------------------------------------------------------------------
 // batched predict_f: its settings, and its results on their way to the host
 // ---------------------------------------------------------------------------------------------

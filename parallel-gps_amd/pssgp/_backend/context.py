@@ -159,6 +159,15 @@ class Context:
                       "pgps_get_chunk")
         return lc.value, nb.value
 
+    def get_batch_chunk(self, n_models, n_steps):
+        """(steps per lane, workgroups per model) of a batched fused call of n_models models over n_steps steps (the merged
+        steps of a predict): gp_ll_batch, the three-launch form of gp_predict_batch, the four-launch road of
+        gp_ll_grad_adj_batch."""
+        lc, nb = c_int(0), c_int(0)
+        _facade.check(self, self.lib.pgps_get_batch_chunk(self.handle, int(n_models), int(n_steps), ctypes.byref(lc),
+                                                          ctypes.byref(nb)), "pgps_get_batch_chunk")
+        return lc.value, nb.value
+
     def set_stream(self, hip_stream_handle):
         """Launch on an external hipStream_t (an integer handle; 0 / None = the HIP null stream)."""
         _facade.check(self, self.lib.pgps_set_stream(self.handle, c_void_p(hip_stream_handle or 0)), "pgps_set_stream")

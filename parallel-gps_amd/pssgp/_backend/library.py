@@ -55,6 +55,7 @@ _SIGNATURES = (
     ("pgps_debug_resident_delay", "PIII"),
     ("pgps_get_geometry", "PLIiii"),
     ("pgps_get_chunk", "PLii"),
+    ("pgps_get_batch_chunk", "PILii"),
     ("pgps_get_family", "PLIIIi"),
     ("pgps_profile_calibrate", "Pd"),
     ("pgps_profile_read", "PdlI"),
