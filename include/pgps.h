@@ -834,6 +834,44 @@ int pgps_gp_panel_laplace_grad_dev_f64(pgps_ctx*, long S, const long* offs, int 
                                        int npars, const double* pars, const double* ts, const double* ys, const double* f,
                                        const double* v, const double* zs, const double* ss, double* out);
 
+/* ---- the hyper-parameter fit of every series of a panel in ONE launch (fused path, fp64, d <= 3) --------
+ * What a survey does with a panel is fit every light curve's own variance, lengthscale and noise variance.  pgps_gp_panel_fit_*
+ * gives every series ONE workgroup that runs the WHOLE search inside the kernel: each evaluation forms the fused model of a
+ * single Matern-1/2, -3/2 or -5/2 kernel (d = 1, 2, 3) in registers from theta = (variance, lengthscales, noise_variance),
+ * runs the three bodies of pgps_gp_panel_ll_grad_* back to back on the series' own scratch and contracts the adjoints to
+ * f = -ll / max(1, n_obs) and its gradient in x = log theta; nothing comes back before the search has ended.  The rule is
+ * csrc/pgps_fit.h: BFGS on the inverse matrix with a backtracking Armijo search (c = 1e-4, at most 21 trials, a trial that is
+ * no descent step is skipped without an evaluation) and projection onto the box lo <= theta <= hi; converged when the
+ * projected gradient's largest component is <= gtol.  At most 1 + 42 max_iter evaluations per series.
+ *   unit     HOST, ONE model row [lam | N1 | N2 | Pinf | H | R] as the panel's tables hold them: the Matern-5/2 SDE at lam = 1,
+ *            variance 1 (F = lam F1, Pinf = s2 P1, H = H1).  Read at d = 3 only (may be NULL at d = 1, 2); R is ignored
+ *   rs       per-observation noise variances (the step's variance is noise_variance + rs[k]), or NULL
+ *   theta0, lo, hi   HOST (S, 3): every series' start and box, in theta
+ *   free3    HOST (3): a coordinate with free3[i] = 0 keeps theta0[s, i] exactly (never through log / exp; lo, hi unread).  A
+ *            fixed noise_variance may be 0 where rs is given
+ *   thetas   (S, 3): the last accepted iterate.  A coordinate that never moved is theta0 bit for bit, one that ended on a bound
+ *            is that bound bit for bit
+ *   info     (S, 8): [ll | ll at the start | iterations | evaluations | status | max |q| | observed rows | 0];  status 0 converged,
+ *            1 max_iter iterations made, 2 the line search failed, 3 f or g not finite at the start (max |q| is then NaN).  A
+ *            series without an observed row returns its start with status 0 and 0 iterations.
+ * The host form takes host arrays and returns PGPS_E_NUMERIC (outputs written) where a series' ll is not finite; the _dev form
+ * takes device pointers for ts, ys, rs, thetas, info, synchronises the context's stream ONCE to copy its tables in and is
+ * asynchronous afterwards.  Steps per lane, groups and bit-repeatability as the pgps_gp_panel_* calls: a row's bits depend on
+ * that series alone.
+ * Profiling: the search kernel has no timer slot of its own; pgps_profile_* charge a whole search to PGPS_K_FILTER_APPLY; the
+ * roctx range is "panel_fit".
+ * Errors (no output is touched): S < 1, a null pointer (unit at d = 3), an empty series, a series above PGPS_PANEL_MAX_STEPS,
+ * lam <= 0 in the unit row at d = 3, a free coordinate whose theta0, lo or hi is not finite and > 0 or whose lo >= hi, a fixed
+ * variance or lengthscale that is not finite and > 0, a fixed noise_variance that is not finite, < 0, or <= 0 without rs, gtol not
+ * finite or < 0, max_iter outside 1 .. 200: PGPS_E_INVALID (the host form also: rs not finite, < 0, or noise_variance + rs <= 0
+ * with a fixed noise_variance, at an observed row); d outside 1..3: PGPS_E_UNSUPPORTED_DIM. */
+int pgps_gp_panel_fit_f64(pgps_ctx*, long S, const long* offs, int d, const double* unit, const double* ts, const double* ys,
+                          const double* rs, const double* theta0, const double* lo, const double* hi, const int* free3,
+                          double gtol, int max_iter, double* thetas /* S 3 */, double* info /* S 8 */);
+int pgps_gp_panel_fit_dev_f64(pgps_ctx*, long S, const long* offs, int d, const double* unit, const double* ts, const double* ys,
+                              const double* rs, const double* theta0, const double* lo, const double* hi, const int* free3,
+                              double gtol, int max_iter, double* thetas /* S 3 */, double* info /* S 8 */);
+
 /* ---- sequential mode: pssgp/kalman/sequential.py:11-73 (kf, ks) ------------------------
  * StateSpaceGP(parallel=False).  Host arithmetic on HOST pointers, as in the reference (its
  * sequential mode is the CPU `tf.scan`).  No context needed.  mps / Pps (predicted moments,

@@ -81,6 +81,27 @@ __device__ __forceinline__ GpArgs<double> gp_panel_select(const PanelArgs& p, co
     return g;
 }
 
+// What the kernels that run a whole search inside one workgroup (k_gpp_newton, pgps_panel_site.hip.h; k_gpp_fit,
+// pgps_panel_fit.hip.h) put between the bodies and read the bodies' totals with.
+// Stores that other lanes of the workgroup read later are drained before the barrier
+__device__ __forceinline__ void wg_sync() {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+}
+
+// A sum every lane already holds with the same bits, moved to scalar registers (the first active lane's copy): the compiler
+// then KNOWS that the search's branches are uniform -- the loops around the barriers become scalar branches, and the swapped
+// pointers stay in scalar registers instead of a vector register pair each
+__device__ __forceinline__ double uniform_word(double x) {
+    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(x)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(x));
+    return __hiloint2double(hi, lo);
+}
+
+// a word another lane of this workgroup stored before the last wg_sync: always a vector load
+__device__ __forceinline__ double site_word(const double* p) {
+    return uniform_word(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+}
+
 // One workgroup per series, grid (1, series of the launch): blockIdx.x stays the workgroup's place inside its series, 0.
 // SMOOTH: 0 = the log-likelihoods, 2 = predict (a series without queries takes the log-likelihood's road: it still returns ll).
 // Every branch below is uniform over the workgroup; there is no early return (every series of a launch has n >= 1).

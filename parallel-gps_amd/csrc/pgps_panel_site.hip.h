@@ -51,23 +51,7 @@ struct PanelSiteArgs {
     double* info;               // (the group's series, kSiteInfo)
 };
 
-__device__ __forceinline__ void wg_sync() {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-}
-
-// A sum every lane already holds with the same bits, moved to scalar registers (the first active lane's copy): the compiler
-// then KNOWS that the search's branches are uniform -- the loops around the barriers become scalar branches, and the swapped
-// pointers stay in scalar registers instead of a vector register pair each
-__device__ __forceinline__ double uniform_word(double x) {
-    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(x)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(x));
-    return __hiloint2double(hi, lo);
-}
-
-// a word another lane of this workgroup stored before the last wg_sync: always a vector load
-__device__ __forceinline__ double site_word(const double* p) {
-    return uniform_word(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-}
+// (wg_sync, uniform_word, site_word: pgps_panel.hip.h)
 
 // the four operations of newton_search on one series' slices
 template <int D>

@@ -106,6 +106,7 @@ _SIGNATURES = (
     ("pgps_gp_panel_profile_grad_dev_f64", "PLPIIPIPPPPPPP"),
     ("pgps_gp_panel_laplace{dev}_f64", "PLPIIPIIPPPDIPPPPP"),
     ("pgps_gp_panel_laplace_grad{dev}_f64", "PLPIIPIIPPPPPPPP"),
+    ("pgps_gp_panel_fit{dev}_f64", "PLPIPPPPPPPPDIPP"),
     # a series kept on the device
     ("pgps_series_create_f64", "PLPPDH"),
     ("pgps_series_set_queries_f64", "PLP"),

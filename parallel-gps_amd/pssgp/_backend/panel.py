@@ -483,3 +483,52 @@ def gp_panel_laplace_predict_dev(data, models, qoffs, tq):
                       dres, dres + 8 * K, None)
         data.ctx.d2h(res, dres)
     return res[:K], res[K:]
+
+
+# -- the hyper-parameter fit of every series (pgps_gp_panel_fit_*) --------------------------------------
+FIT_INFO = ("ll", "ll_start", "iterations", "evaluations", "status", "grad_norm", "n_obs", "reserved")
+FIT_PARAMETERS = 3              # kFitP of csrc/pgps_fit.h: variance, lengthscales, noise_variance
+
+
+def _fit_arguments(S, unit, theta0, lo, hi, free):
+    """The host arrays of a fit call: the unit row (or None), theta0 / lo / hi (S, 3) and free (3,) int32."""
+    out = []
+    for name, a in (("theta0", theta0), ("lo", lo), ("hi", hi)):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != (S, FIT_PARAMETERS):
+            raise ValueError(f"{name} must be ({S}, {FIT_PARAMETERS}), got shape {a.shape}")
+        out.append(a)
+    f = np.ascontiguousarray(free, dtype=np.int32).reshape(-1)
+    if f.shape[0] != FIT_PARAMETERS:
+        raise ValueError(f"free must hold {FIT_PARAMETERS} flags, got {f.shape[0]}")
+    u = None if unit is None else np.ascontiguousarray(unit, dtype=np.float64).reshape(-1)
+    return [u] + out + [f]
+
+
+def gp_panel_fit(d, unit, offs, ts, ys, rs, theta0, lo, hi, free, gtol=1e-6, max_iter=100, device=0):
+    """The fit of every series of a panel in one launch per group (pgps_gp_panel_fit_f64), host arrays: (thetas (S, 3), info
+    (S, 8) in the order of FIT_INFO).  d = 1, 2, 3: Matern-1/2, -3/2, -5/2; `unit`: one model row, the Matern-5/2 SDE at lam = 1
+    and variance 1 (None at d < 3); theta0, lo, hi (S, 3) in theta = (variance, lengthscales, noise_variance); free (3,) flags."""
+    o, ts_a, ys_a, rs_a = _inputs(offs, ts, ys, rs)
+    S = o.shape[0] - 1
+    u, t0, lo_a, hi_a, f = _fit_arguments(S, unit, theta0, lo, hi, free)
+    thetas, info = np.empty((S, FIT_PARAMETERS), np.float64), np.empty((S, len(FIT_INFO)), np.float64)
+    ctx = _require(get_context(device), "pgps_gp_panel_fit_f64", "pgps_gp_panel_fit_*")
+    ctx.call("pgps_gp_panel_fit_f64", S, _ptr(o), int(d), _ptr(u), _ptr(ts_a), _ptr(ys_a), _ptr(rs_a), _ptr(t0), _ptr(lo_a),
+             _ptr(hi_a), _ptr(f), float(gtol), int(max_iter), _ptr(thetas), _ptr(info))
+    return thetas, info
+
+
+def gp_panel_fit_dev(data, d, unit, theta0, lo, hi, free, gtol=1e-6, max_iter=100):
+    """gp_panel_fit on the resident series of `data` (pgps_gp_panel_fit_dev_f64): [thetas | info] come back in one copy."""
+    _require(data.ctx, "pgps_gp_panel_fit_dev_f64", "pgps_gp_panel_fit_*")
+    S = data.S
+    u, t0, lo_a, hi_a, f = _fit_arguments(S, unit, theta0, lo, hi, free)
+    nt = S * FIT_PARAMETERS
+    res = np.empty(nt + S * len(FIT_INFO), np.float64)
+    with data.ctx.lock:
+        dres = data._buffer("fit", res.nbytes)
+        data.ctx.call("pgps_gp_panel_fit_dev_f64", S, _ptr(data.offs), int(d), _ptr(u), data.ts, data.ys, data.rs, _ptr(t0),
+                      _ptr(lo_a), _ptr(hi_a), _ptr(f), float(gtol), int(max_iter), dres, dres + 8 * nt)
+        data.ctx.d2h(res, dres)
+    return res[:nt].reshape(S, FIT_PARAMETERS), res[nt:].reshape(S, len(FIT_INFO))

@@ -15,6 +15,7 @@ import numpy as np
 from . import _backend, config
 from .gradients import mask_wrt
 from .model import StateSpaceGP
+from .panel_fit import PanelFitting
 from .panel_trend import PanelTrend
 
 
@@ -27,7 +28,7 @@ def _column(a, what, s):
     return a
 
 
-class StateSpaceGPPanel(PanelTrend):
+class StateSpaceGPPanel(PanelTrend, PanelFitting):
     """StateSpaceGPPanel(series, kernel, noise_variance=1.0, parallel=True, observation_variances=None, mean_function=None).
 
     series: a list of S pairs (t_i, y_i), each (n_i,) or (n_i, 1), n_i >= 1; NaN in y is a missing observation.  Times in any
