@@ -153,6 +153,10 @@ int pgps_get_chunk(pgps_ctx* ctx, long n_steps, int* steps_per_lane, int* n_work
  * lane -- pgps_set_chunk's value, else 16 while B x workgroups >= 1024, halved towards 4 -- and the 256-lane workgroups per
  * model by it.  Read-only.  Errors: B < 1, n_steps < 1, a null pointer: PGPS_E_INVALID. */
 int pgps_get_batch_chunk(pgps_ctx* ctx, int B, long n_steps, int* steps_per_lane, int* n_workgroups);
+/* What a panel launch (pgps_gp_panel_*: one 256-lane workgroup per series) gives a series of m steps -- counted MERGED, n + k,
+ * in predict: steps per lane -- the series' own, max(1, ceil(m / 256)), or pgps_set_chunk's value where it covers the series
+ * (chunk x 256 >= m).  Read-only.  Errors: m < 1, m > PGPS_PANEL_MAX_STEPS, a null pointer: PGPS_E_INVALID. */
+int pgps_get_panel_chunk(pgps_ctx* ctx, long m, int* steps_per_lane);
 /* Which kernel family a pkf (what = 0) / pks (1) / pkfs (2) call -- or a phase of the segment protocol (3) -- of n_steps at
  * state dimension d will run on under the context's settings (float32 arithmetic if f32 != 0; a float32 smoother call that
  * is promoted to fp64 arithmetic, pgps_set_f32_policy, takes the fp64 answer): what a benchmark needs to name the kernels it

@@ -4,6 +4,7 @@
 #include <new>
 
 #include "pgps_host.h"
+#include "pgps_scratch.h"
 
 using namespace pgps;
 
@@ -531,6 +532,12 @@ extern "C" int pgps_get_batch_chunk(pgps_ctx* ctx, int B, long N, int* Lc, int* 
     if (!ctx || B < 1 || N < 1 || !Lc || !nb) return PGPS_E_INVALID;
     *Lc = batch_steps_per_lane(ctx, B, N);
     *nb = (int)((N + (long)kBlock * *Lc - 1) / ((long)kBlock * *Lc));
+    return PGPS_OK;
+}
+// ... and of a panel launch (one workgroup per series): panel_steps_per_lane, the rule of every panel planner (pgps_scratch.h)
+extern "C" int pgps_get_panel_chunk(pgps_ctx* ctx, long m, int* Lc) {
+    if (!ctx || m < 1 || m > PGPS_PANEL_MAX_STEPS || !Lc) return PGPS_E_INVALID;
+    *Lc = panel_steps_per_lane(m, ctx->chunk);
     return PGPS_OK;
 }
 // ---------------------------------------------------------------------------------------------

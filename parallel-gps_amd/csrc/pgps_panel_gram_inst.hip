@@ -69,9 +69,7 @@ void panel_gram_plan(const pgps_ctx* ctx, const PanelGramCall& c, PanelGramPlan&
         r.row0 = c.offs[s];
         r.n = (int)(c.offs[s + 1] - c.offs[s]);
         r.m = r.n;
-        // steps per lane: the series' own, max(1, ceil(n / kBlock)); a pinned chunk (pgps_set_chunk) where it covers the series
-        const int own = (r.n + kBlock - 1) / kBlock;
-        r.Lc = (ctx->chunk > 0 && (long)ctx->chunk * kBlock >= (long)r.n) ? ctx->chunk : (own < 1 ? 1 : own);
+        r.Lc = panel_steps_per_lane(r.n, ctx->chunk);
         r.model = c.nmodels == 1 ? 0 : (int)s;
         const size_t w = panel_pad((size_t)r.n * (size_t)c.C);
         const bool open = !groups.empty() && groups.back().series < kGridYMax && bytes_of(groups.back().w + w) <= budget;

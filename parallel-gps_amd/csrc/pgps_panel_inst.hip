@@ -49,6 +49,7 @@ int launch_panel_merge(pgps_ctx* ctx, const PanelArgs& p, unsigned tiles, unsign
 #endif
 
 static inline size_t panel_pad(size_t n) { return align_up(n, (size_t)kPanelAlign); }
+static_assert(kPanelLanes == kBlock, "panel_steps_per_lane counts the lanes of the panel's one workgroup");
 
 template <int D>
 struct PanelParts {
@@ -96,9 +97,7 @@ void panel_plan(const pgps_ctx* ctx, const PanelCall& c, PanelWhat what, PanelPl
         r.q0 = predict ? c.qoffs[s] : 0;
         r.k = predict ? (int)(c.qoffs[s + 1] - c.qoffs[s]) : 0;
         r.m = r.n + r.k;
-        // steps per lane: the series' own, max(1, ceil(m / kBlock)); a pinned chunk (pgps_set_chunk) where it covers the series
-        const int own = (r.m + kBlock - 1) / kBlock;
-        r.Lc = (ctx->chunk > 0 && (long)ctx->chunk * kBlock >= (long)r.m) ? ctx->chunk : (own < 1 ? 1 : own);
+        r.Lc = panel_steps_per_lane(r.m, ctx->chunk);
         r.model = c.nmodels == 1 ? 0 : (int)s;
         const size_t merged = r.k > 0 ? panel_pad((size_t)r.m) : 0;
         // the filtered moments the smoother reads back: of the merged series, and in the predictive checks of EVERY series

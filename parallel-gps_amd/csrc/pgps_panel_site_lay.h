@@ -27,12 +27,9 @@ constexpr SiteRecLens site_rec_lens(int d) {
     return {d * d + d + d * (d + 1) + d, d * d + d + d * (d + 1) / 2, d + d * (d + 1) / 2, d * d + 2 * d + 1};
 }
 
-// steps per lane of a series of n rows: its own, max(1, ceil(n / lanes)); the pinned chunk wherever it covers the series
-inline int site_steps_per_lane(int n, int chunk) {
-    const int own = (n + kSiteLanes - 1) / kSiteLanes;
-    if (chunk > 0 && (long)chunk * kSiteLanes >= (long)n) return chunk;
-    return own < 1 ? 1 : own;
-}
+// steps per lane of a series of n rows: the panel's rule (pgps_scratch.h)
+static_assert(kSiteLanes == kPanelLanes, "panel_steps_per_lane counts the lanes of a series' one workgroup");
+inline int site_steps_per_lane(int n, int chunk) { return panel_steps_per_lane(n, chunk); }
 
 // element counts of a group
 struct SiteTotals {

@@ -52,6 +52,16 @@ inline size_t batch_group(size_t budget, size_t fixed_bytes, size_t per_item_byt
     return group < 1 ? 1 : group;
 }
 
+// Steps per lane of a launch that gives a series of m steps ONE workgroup of kPanelLanes lanes (the panel kernels, their Gram,
+// site and fit launches): the series' own, max(1, ceil(m / lanes)); the pinned chunk (pgps_set_chunk) where it covers the
+// series (ctx->chunk * kBlock >= m).  THE rule: every planner and pgps_get_panel_chunk call it
+constexpr int kPanelLanes = 256;        // == kBlock (pgps_panel_inst.hip asserts it)
+inline int panel_steps_per_lane(long m, int chunk) {
+    if (chunk > 0 && (long)chunk * kPanelLanes >= m) return chunk;
+    const long own = (m + kPanelLanes - 1) / kPanelLanes;
+    return own < 1 ? 1 : (int)own;
+}
+
 // The budgets when pgps_set_batch_scratch has not set one.
 // Fused path (d <= 3): the smallest budget beyond which the measured time per model no longer improves (B = 1000,
 // N + K = 5000, d = 2: 3.79, 2.83, 2.35, 2.19 ms at 8, 16, 32, 64 MiB, 2.2 .. 2.7 ms at 256 MiB and 1 GiB)

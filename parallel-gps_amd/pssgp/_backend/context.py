@@ -168,6 +168,13 @@ class Context:
                                                           ctypes.byref(nb)), "pgps_get_batch_chunk")
         return lc.value, nb.value
 
+    def get_panel_chunk(self, n_steps):
+        """Steps per lane a panel launch (one workgroup per series) gives a series of n_steps steps, the merged steps of a
+        predict: its own, or the pinned set_chunk where that covers the series."""
+        lc = c_int(0)
+        _facade.check(self, self.lib.pgps_get_panel_chunk(self.handle, int(n_steps), ctypes.byref(lc)), "pgps_get_panel_chunk")
+        return lc.value
+
     def set_stream(self, hip_stream_handle):
         """Launch on an external hipStream_t (an integer handle; 0 / None = the HIP null stream)."""
         _facade.check(self, self.lib.pgps_set_stream(self.handle, c_void_p(hip_stream_handle or 0)), "pgps_set_stream")

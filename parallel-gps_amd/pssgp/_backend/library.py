@@ -56,6 +56,7 @@ _SIGNATURES = (
     ("pgps_get_geometry", "PLIiii"),
     ("pgps_get_chunk", "PLii"),
     ("pgps_get_batch_chunk", "PILii"),
+    ("pgps_get_panel_chunk", "PLi"),
     ("pgps_get_family", "PLIIIi"),
     ("pgps_profile_calibrate", "Pd"),
     ("pgps_profile_read", "PdlI"),
